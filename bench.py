@@ -11,6 +11,9 @@ metric = audio-seconds / second (whole job, all GPUs).  Weak scaling: per-GPU ba
                                                         under torch.distributed.run, one rank per GPU, 127.0.0.1 rendezvous)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W   (the same thing)
   python bench.py --gpus 2 --dry-launch                 (no GPU needed: spawns the ranks on gloo and prints what each one sees)
+  python bench.py ... --dump-outputs DIR                (also writes the last timed job's waveform as DIR/waveform.npy: the
+                                                        inputs are seeded, so two builds run with the same arguments compare
+                                                        output for output)
 
 The headline runs in the library's DEFAULT product mode, "bf16x6": fp32 storage / accumulation, every product evaluated as 6 bf16
 MFMA partial products of exact 3-part operand splits — fp32-grade (2.4e-7 rms per contraction; the fp32 MFMA itself: 2.1e-7), i.e.
@@ -136,7 +139,35 @@ def parse():
                     help="launcher check without a GPU: spawn --gpus ranks (gloo), rendezvous, shard the global batch, print ONE "
                          "JSON line listing every rank; no kernels run")
     ap.add_argument("--master-port", type=int, default=0, help="rendezvous port of the self-launch (default: a free one)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed job returned (the global batch's waveform) as "
+                         "DIR/<name>.npy, float32, at most 64 MB in all (a fixed seeded sample of a larger output)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """`--dump-outputs`: every array as `out_dir/<name>.npy` (float64 stays float64, anything else becomes float32).  Above
+    DUMP_LIMIT_BYTES in all, each array is replaced by the same share of its flattened elements at indices drawn by a fixed seed
+    (sorted), so that the sample depends only on the array's shape and two builds can be compared element for element."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64 if np.asarray(v).dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    budget = DUMP_LIMIT_BYTES - 4096 * len(arrays)   # room for the .npy headers
+    for name, a in arrays.items():
+        what = f"{name} {tuple(a.shape)} {a.dtype}"
+        if total > budget:
+            n = max(1, a.size * budget // total)
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=n, replace=False))
+            a = a.reshape(-1)[idx]
+            what += f": {n} elements sampled (seed 0)"
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+        print(f"bench.py: wrote {os.path.join(out_dir, name + '.npy')} ({what})", file=sys.stderr, flush=True)
 
 
 def _free_port():
@@ -588,6 +619,13 @@ def main():
         per_rank = [round(float(t.item()), 4) for t in every]
         dt = max(per_rank)                                 # contract: MAX over ranks
     assert wav.shape[:2] == (B, 1) and np.isfinite(wav).all()
+    if args.dump_outputs:   # outside the timed window: the last timed job's waveform, every rank's prompts in global order
+        shards = [wav]
+        if world > 1:
+            shards = [None] * world
+            torch.distributed.all_gather_object(shards, wav)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"waveform": np.concatenate(shards, axis=0)})
     audio_seconds = wav.shape[-1] / float(ld.sampling_rate)  # delivered audio per prompt (10.24 s)
     khz = ld.sampling_rate // 1000
 

@@ -14,8 +14,8 @@ How it is pinned (the reference ships no tests, no golden vectors — SURVEY.md 
     container (import stubs of SURVEY.md Appendix A), loads the same deterministic weights
     (`oracle/weights.py`) and writes input/output fixtures to `tests/golden/*.npz`;
   * `tests/test_oracle.py` checks this restatement against those fixtures on the CPU
-    (runs everywhere, no reference needed) and `tests/test_oracle_vs_reference.py` checks it
-    against the live reference classes when /root/reference is present.
+    (runs everywhere, no reference needed) and `tests/test_oracle_vs_reference.py` checks it against what
+    the reference classes computed on other weights, shapes and seeds (`make_golden.py crosscheck`).
   * third-party arithmetic not vendored by the reference: `librosa==0.9.2` mel filterbank /
     pad_center (stft.py:5-6,42,145-147) is restated from its published definition in
     `oracle/stft.py` — parity unpinned for that piece (no librosa offline, no reference test); the restated basis is

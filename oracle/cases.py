@@ -27,6 +27,8 @@ UNET_FILM_TINY = {"image_size": 64, "extra_film_condition_dim": 512, "context_di
                   "out_channels": 16, "model_channels": 128, "attention_resolutions": [2, 1],
                   "num_res_blocks": 1, "channel_mult": [1, 2], "num_head_channels": 32,
                   "use_spatial_transformer": True, "transformer_depth": 1}
+# (cfg, B, H, W, t5 length, seed) of the oracle cross-check on inputs outside the other fixtures (tests/golden/crosscheck.npz)
+UNET_CROSSCHECK = [(UNET_TINY, 3, 24, 8, 5, 11), (UNET_LARGE_TINY, 1, 16, 16, 20, 12), (UNET_FILM_TINY, 2, 16, 8, 0, 13)]
 
 
 UNET_48K = {"image_size": 64, "extra_film_condition_dim": 512, "context_dim": [None], "in_channels": 16,
@@ -149,6 +151,11 @@ def seqgen_cond(cfg: dict, B: int, T: int, seed: int = 5) -> dict:
 
 # --- VITS phoneme encoder (second half; config 5) --------------------------------------------
 PHONEME = {"vocabs_size": 183, "pad_token_id": 0, "pad_length": 310}   # utils.py:156-165
+# the oracle cross-check (tests/golden/crosscheck.npz) runs the phoneme encoder at a shorter pad length than the other fixtures,
+# with these id lengths (t5_crosscheck_config: the T5 geometry it uses, and its token lengths)
+PHONEME_CROSSCHECK = dict(PHONEME, pad_length=32)
+PHONEME_CROSSCHECK_LENGTHS = (32, 11, 1)
+T5_CROSSCHECK_LENGTHS = (9, 17, 2)
 
 
 def phoneme_state_dict(shapes: dict, seed: int = 0) -> dict:
@@ -184,6 +191,14 @@ def t5_test_config() -> dict:
     from .t5 import FLAN_T5_LARGE
     c = dict(FLAN_T5_LARGE)
     c.update(vocab_size=512, num_layers=3)
+    return c
+
+
+def t5_crosscheck_config() -> dict:
+    """A narrower T5 than t5_test_config (d_model 256, 4 heads x 64, d_ff 704; same buckets, gating and layer count) for the
+    oracle cross-check on a geometry no other fixture uses."""
+    c = t5_test_config()
+    c.update(d_model=256, num_heads=4, d_ff=704)
     return c
 
 

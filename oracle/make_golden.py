@@ -1,6 +1,6 @@
 """Generate tests/golden/*.npz by running the REAL reference (imported from /root/reference with the
 import stubs of oracle/refimport.py) on the seeded cases of oracle/cases.py.  TEST INFRA ONLY; run
-in the build container:  python -m oracle.make_golden [all|unet|vae|hifigan|ddim|stft|e2e5|masked|ancestral|e2e200]
+in the build container:  python -m oracle.make_golden [all|unet|vae|hifigan|ddim|stft|e2e5|masked|ancestral|e2e200|crosscheck|...]
 
 The reference ships no golden vectors; these fixtures are what pins both the oracle
 restatement (tests/test_oracle.py, CPU) and the HIP product (tests/test_*_gpu.py) to the reference.
@@ -526,6 +526,167 @@ def gen_ancestral(T: int, B: int, name: str):
     save(name, latent=z, first=inter[1])
 
 
+def gen_crosscheck():
+    """tests/test_oracle_vs_reference.py: the REAL classes on weights / shapes / seeds that no other fixture uses, with the
+    state-dict shapes each class holds (`<case>_shapes`, JSON) so that the test rebuilds the same name-keyed weights without the
+    reference."""
+    out = {}
+
+    def shapes(d):   # UTF-8 bytes of the JSON (a numpy str array would spend 4 bytes per character)
+        return np.frombuffer(json.dumps({k: list(v) for k, v in d.items()}).encode(), dtype=np.uint8)
+
+    U = refimport.unet_cls()
+    for i, (cfg, B, H, W, t5, seed) in enumerate(cases.UNET_CROSSCHECK):
+        ref = U(**cfg).eval()
+        load_det(ref, seed)
+        x, t, ctxs, masks, y = cases.unet_inputs(cfg, B, H, W, max(t5, 1), seed=seed)
+        out[f"unet{i}"] = ref(x, t, y=y, context_list=ctxs, context_attn_mask_list=masks)
+        out[f"unet{i}_shapes"] = shapes(weights.shapes_of(ref))
+    from audioldm2.latent_encoder.autoencoder import AutoencoderKL
+    dd = cases.DDCONFIG_16K
+    ae = AutoencoderKL(ddconfig=dd, embed_dim=dd["z_channels"], image_key="fbank").eval()
+    load_det(ae, 21)
+    out["vae_shapes"] = shapes(weights.shapes_of(ae))
+    out["vae_decode"] = ae.decode(cases.latent_input(1, 8, 12, 16, seed=21))
+    out["vae_moments"] = ae.encode(cases.mel_input(1, 64, 64, seed=22).permute(0, 2, 1)[:, None]).parameters
+    g = refimport.hifigan_generator(dict(cases.HIFIGAN_16K))
+    load_det(g, 31)
+    out["hifigan_shapes"] = shapes(weights.shapes_of(g))
+    out["hifigan"] = g(cases.mel_input(2, 64, 12, seed=31))
+    # inpainting front-end helpers (utilities/audio/tools.py)
+    import audioldm2.utilities.audio.tools as rt
+    w = np.random.default_rng(0).standard_normal(500).astype(np.float32) * 0.3 + 0.1
+    out["normalize_wav"] = rt.normalize_wav(w)
+    for seg in (None, 500, 800):
+        out[f"pad_wav_{seg}"] = rt.pad_wav(w[None], seg)
+    fb = torch.randn(20, 65, generator=torch.Generator().manual_seed(0))
+    for tl in (24, 16):
+        out[f"pad_spec_{tl}"] = rt._pad_spec(fb, tl)
+    # sequence generator: other batch, lengths, seed
+    cfg = dict(cases.SEQGEN_FULL, steps=5)
+    m = refimport.sequence_generator(cfg["steps"], cfg["keys"], cfg["dims"])
+    sh = {k: tuple(v.shape) for k, v in m.state_dict().items() if k != "model.wte.weight"}
+    m.load_state_dict(weights.make_state_dict(sh, seed=3), strict=False)
+    out["seqgen_shapes"] = shapes(sh)
+    out["seqgen"], _ = m.generate(None, cond_dict=cases.seqgen_cond(cfg, 2, 9, seed=21))
+    # HTSAT: other weights, one 6 s clip, depths (1, 2, 1, 2)
+    from oracle import htsat as oh
+    hc = dict(cases.htsat_test_config(), depths=(1, 2, 1, 2))
+    ac = dict(oh.AUDIO_CFG)
+    m = refimport.htsat_swin_transformer(hc, ac)
+    skip = ("relative_position_index", "attn_mask", "num_batches_tracked", "tscam_conv", "head.")
+    sh = {"audio_branch." + k: tuple(v.shape) for k, v in m.state_dict().items() if not any(t in k for t in skip)}
+    sd = cases.htsat_state_dict(sh, seed=5)
+    missing = m.load_state_dict({k[len("audio_branch."):]: v for k, v in sd.items()}, strict=False)
+    assert all(any(t in k for t in skip) for k in missing.missing_keys) and not missing.unexpected_keys
+    out["htsat_shapes"] = shapes(sh)
+    wav48 = oh.resample(cases.clap_waveform(1, seed=33), 16000, 48000)[:, :288000]
+    out["htsat"] = m({"waveform": wav48}, device="cpu")["embedding"]
+    # VITS phoneme encoder and FLAN-T5 encoder: other weights, ids and lengths
+    pc = cases.PHONEME_CROSSCHECK
+    m = refimport.phoneme_encoder(**pc)
+    sh = {k: tuple(v.shape) for k, v in m.state_dict().items()}
+    m.load_state_dict(cases.phoneme_state_dict(sh, seed=4), strict=True)
+    out["phoneme_shapes"] = shapes(sh)
+    ids_g = torch.Generator().manual_seed(17)
+    idx = torch.randint(1, pc["vocabs_size"], (3, pc["pad_length"]), generator=ids_g)
+    for b, n in enumerate(cases.PHONEME_CROSSCHECK_LENGTHS):
+        idx[b, n:] = pc["pad_token_id"]
+    out["phoneme_emb"], out["phoneme_mask"] = m(idx)
+    tcfg = cases.t5_crosscheck_config()
+    L = max(cases.T5_CROSSCHECK_LENGTHS)
+    ids = torch.randint(3, tcfg["vocab_size"], (3, L), generator=ids_g)
+    am = torch.zeros(3, L, dtype=torch.long)
+    for b, n in enumerate(cases.T5_CROSSCHECK_LENGTHS):
+        ids[b, n - 1] = 1
+        ids[b, n:] = 0
+        am[b, :n] = 1
+    ref = refimport.flan_t5_hidden_state(tcfg, lambda prompt: (ids, am))
+    sh = {k: tuple(v.shape) for k, v in ref.model.state_dict().items()}
+    ref.model.load_state_dict(cases.t5_state_dict(sh, seed=6), strict=True)
+    out["t5_shapes"] = shapes(sh)
+    out["t5_hidden"], out["t5_mask"] = ref(["x", "y", "z"])
+    path = os.path.join(OUT, "crosscheck.npz")
+    np.savez_compressed(path, **{k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in out.items()})
+    print(f"  wrote {path} ({os.path.getsize(path)/1024:.0f} KiB)")
+
+
+HOST_NAMES = ("audioldm2-full", "audioldm2-full-large-1150k", "audioldm2-speech-gigaspeech", "audioldm_48k")
+PHONEME_STRINGS = ("", "həlˈoʊ wˈɜːld, ðɪs ɪz ɐ tˈɛst!", "it's 'quoted' § unknown", "a" * 400)
+
+
+def save_wave_cases():
+    """(waveform, name) cases of tests/test_host_logic.py::test_save_wave_names_files_like_the_reference."""
+    rng = np.random.default_rng(0)
+    return [(rng.uniform(-0.5, 0.5, (3, 1, 1600)).astype(np.float32), "outwav"),
+            (rng.uniform(-0.5, 0.5, (1, 1, 800)).astype(np.float32), "a dog barking"),
+            (rng.uniform(-0.5, 0.5, (2, 1, 800)).astype(np.float32), ["x/first.wav", "second"]),
+            (rng.uniform(-0.5, 0.5, (1, 1, 800)).astype(np.float32), "y" * 300)]
+
+
+def gen_reference_host():
+    """Host-side results of the REAL reference for the CPU tests: its config dicts (reference_configs.json, utils.py:116-561),
+    the file names utils.save_wave picks, phoneme ids and the text-to-audio batch (reference_host.npz), and the schedule /
+    conditioning methods of its LatentDiffusion on seeded inputs (tests/test_reference_binding.py)."""
+    refimport.install()
+    import audioldm2.latent_diffusion.models.ddpm as rddpm
+    import audioldm2.utils as ru
+    from audioldm2.latent_diffusion.util import get_vits_phoneme_ids_no_padding as ref_ids
+    from audioldm2.pipeline import make_batch_for_text_to_audio as ref_batch
+    os.makedirs(OUT, exist_ok=True)
+    with open(os.path.join(OUT, "reference_configs.json"), "w") as f:
+        json.dump({name: ru.default_audioldm_config(name) for name in HOST_NAMES}, f, indent=0, sort_keys=False)
+    out = {}
+    import tempfile
+    written = []
+    ru.sf.write = lambda path, data, samplerate: written.append(path)
+    with tempfile.TemporaryDirectory() as d:
+        for w, n in save_wave_cases():
+            ru.save_wave(w, d, name=n, samplerate=16000)
+        # a file name longer than 255 characters becomes hex(hash(<name>.wav)): per-process, recorded as "<hash>"
+        rel = [os.path.relpath(p, d).replace(hex(hash("y" * 300 + ".wav")), "<hash>") for p in written]
+        out["save_wave_paths"] = np.array(json.dumps(rel))
+    for i, s in enumerate(PHONEME_STRINGS):
+        out[f"phoneme_ids{i}"] = ref_ids([s] * 3)["phoneme_idx"]
+    rb = ref_batch("a dog barking", batchsize=2)
+    out["batch_tensors"] = np.array(json.dumps([k for k, v in rb.items() if torch.is_tensor(v)]))
+    out["batch_other"] = np.array(json.dumps({k: v for k, v in rb.items() if not torch.is_tensor(v)}))
+    for k, v in rb.items():
+        if torch.is_tensor(v):
+            out[f"batch_{k}"] = v
+    # LatentDiffusion schedule and conditioning methods (ddpm.py:357-373, 430-436, 804-828, 958-971)
+    rp = ru.default_audioldm_config("audioldm2-full")["model"]["params"]
+    rp["unet_config"]["target"] = "audioldm2_amd.unet.UNetModel"
+    rp["first_stage_config"]["target"] = "audioldm2_amd.vae.AutoencoderKL"
+    rp["cond_stage_config"] = cases.e2e_cond_config("cpu")
+    rp["device"] = "cpu"
+    ref = rddpm.LatentDiffusion(**rp).eval()
+    g = torch.Generator().manual_seed(0)
+    x0, xt, eps = (torch.randn(3, 8, 16, 16, generator=g) for _ in range(3))
+    t = torch.tensor([0, 417, 999])
+    out["q_sample"] = ref.q_sample(x0, t, eps)
+    out["predict_start_from_noise"] = ref.predict_start_from_noise(xt, t, eps)
+    for i, a in enumerate(ref.q_posterior(x0, xt, t)):
+        out[f"q_posterior{i}"] = a
+    torch.manual_seed(7)
+    out["q_sample_drawn"] = ref.q_sample(x0, t)
+    batch = cases.e2e_batch(2)
+    keys = list(ref.cond_stage_model_metadata)
+    out["uncond_keys"] = np.array(json.dumps(keys))
+    for key in keys:
+        meta = ref.cond_stage_model_metadata[key]
+        xc = batch if meta["cond_stage_key"] == "all" else batch[meta["cond_stage_key"]]
+        u = ref.get_learned_conditioning(xc, key, unconditional_cfg=True)
+        for j, v in enumerate(list(u) if isinstance(u, (list, tuple)) else [u]):
+            out[f"uncond_{key}_{j}"] = v
+    d = {k: torch.zeros(1) for k in keys}
+    d["noise"] = torch.ones(1)
+    out["filter_useful_keys"] = np.array(json.dumps(list(ref.filter_useful_cond_dict(d).keys())))
+    path = os.path.join(OUT, "reference_host.npz")   # compressed: the batch's spectrogram placeholders are zeros
+    np.savez_compressed(path, **{k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in out.items()})
+    print(f"  wrote {path} ({os.path.getsize(path)/1024:.0f} KiB)")
+
+
 if __name__ == "__main__":
     what = sys.argv[1:] or ["all"]
     torch.set_grad_enabled(False)
@@ -582,3 +743,7 @@ if __name__ == "__main__":
         gen_e2e_named("audioldm2-full-large-1150k", 5, 8, "e2e_large_5step_b8", "e2elarge_statedict_keys.json")
     if "e2e200" in what:
         gen_e2e(200, 1, "e2e_full_200step_b1")
+    if "all" in what or "crosscheck" in what:
+        gen_crosscheck()
+    if "all" in what or "host" in what:
+        gen_reference_host()

@@ -10,8 +10,8 @@ everything it reaches, as pure functions over a state dict that uses the referen
   CrossAttention.forward       modules/attention.py:343-367
   GEGLU / FeedForward          modules/attention.py:37-63
   timestep_embedding           diffusionmodules/util.py:172-196
-Pinned against the real classes by tests/golden (oracle/make_golden.py) and, when /root/reference
-exists, tests/test_oracle_vs_reference.py.
+Pinned against the real classes by tests/golden (oracle/make_golden.py), on other weights and shapes too
+(tests/test_oracle_vs_reference.py).
 """
 from __future__ import annotations
 

@@ -1,9 +1,7 @@
-"""The reference-side binding of INTEGRATION.md §2, EXECUTED (VERDICT r1 "what's weak" #1):
+"""The reference-side binding of INTEGRATION.md §2 (VERDICT r1 "what's weak" #1):
 
- (a) CPU, build container only (skipped where /root/reference is absent): the REAL
-     `audioldm2.latent_diffusion.models.ddpm.LatentDiffusion` (ddpm.py:640) is constructed through the reference's own
-     `instantiate_from_config` (utils.py:95-114) with the two `target` strings of INTEGRATION.md swapped in and
-     `ddpm.DDIMSampler` rebound; a reference-shaped state dict strict-loads; the module tree is ours.
+ (a) CPU: the schedule and conditioning methods of our LatentDiffusion are bit-equal to the REAL reference class's on the same
+     inputs (its results recorded by `oracle/make_golden.py host`).
  (b) GPU: `audioldm2_amd.ddim.DDIMSampler` driven by a model that exposes ONLY what the reference's LatentDiffusion
      offers a sampler (`apply_model`, `num_timesteps`, `alphas_cumprod`; no `apply_model_cfg` / `prepare_cfg`), i.e. the
      two-sequential-pass CFG fallback the reference's own class would hit (ddim.py:293-296), against the reference
@@ -15,67 +13,13 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import cases, refimport, weights
+from oracle import cases, weights
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def _rms(a):
     return float(np.sqrt(np.mean(np.square(np.asarray(a, dtype=np.float64)))))
-
-
-@pytest.mark.skipif(not refimport.available(), reason="needs the reference checkout (build container only)")
-def test_real_reference_latent_diffusion_builds_on_our_targets_and_strict_loads():
-    refimport.install()
-    import audioldm2.latent_diffusion.models.ddpm as rddpm
-    import audioldm2.utils as ru
-
-    import audioldm2_amd.ddim as addim
-    import audioldm2_amd.hifigan as ahifigan
-    import audioldm2_amd.unet as aunet
-    import audioldm2_amd.vae as avae
-    P = ru.default_audioldm_config("audioldm2-full")["model"]["params"]
-    assert P["unet_config"]["target"].endswith("openaimodel.UNetModel")          # utils.py:329
-    assert P["first_stage_config"]["target"].endswith("autoencoder.AutoencoderKL")  # utils.py:275
-    P["unet_config"]["target"] = "audioldm2_amd.unet.UNetModel"                  # INTEGRATION.md §2, string 1
-    P["first_stage_config"]["target"] = "audioldm2_amd.vae.AutoencoderKL"        # string 2
-    P["cond_stage_config"] = cases.e2e_cond_config("cpu")
-    P["device"] = "cpu"
-    saved = rddpm.DDIMSampler
-    rddpm.DDIMSampler = addim.DDIMSampler                                        # the rebinding (ddpm.py:19, :1437)
-    try:
-        torch.manual_seed(0)
-        ld = rddpm.LatentDiffusion(**P).eval()
-        # the module tree is ours, reached through the reference's own plugin seam
-        assert type(ld).__module__ == "audioldm2.latent_diffusion.models.ddpm"
-        assert isinstance(ld.model.diffusion_model, aunet.UNetModel)
-        assert isinstance(ld.first_stage_model, avae.AutoencoderKL)
-        assert isinstance(ld.first_stage_model.vocoder, ahifigan.Generator)
-        # state-dict compatibility: exactly the reference's hot-path keys and shapes, strict load of a checkpoint-shaped
-        # dict (pipeline.py:172-174 loads checkpoint["state_dict"] this way)
-        with open(os.path.join(GOLD, "e2e_statedict_keys.json")) as f:
-            ref_shapes = {k: tuple(v) for k, v in json.load(f).items()}
-        sd = ld.state_dict()
-        hot = {k: tuple(v.shape) for k, v in sd.items()
-               if k.startswith("model.diffusion_model.") or k.startswith("first_stage_model.")}
-        assert hot == ref_shapes
-        new = weights.make_state_dict(ref_shapes, seed=0)
-        full = dict(sd)
-        full.update(new)
-        ld.load_state_dict(full, strict=True)
-        w = ld.model.diffusion_model.input_blocks[1][0].in_layers[2].weight
-        assert torch.equal(w, new["model.diffusion_model.input_blocks.1.0.in_layers.2.weight"])
-        # sample_log builds the sampler by NAME from ddpm's globals (ddpm.py:1437): it is ours now, and it accepts the
-        # reference model (which has no apply_model_cfg -> the two-pass CFG fallback, covered on the GPU below)
-        s = rddpm.DDIMSampler(ld)
-        assert isinstance(s, addim.DDIMSampler) and not hasattr(ld, "apply_model_cfg")
-        s.make_schedule(ddim_num_steps=200, ddim_eta=1.0, verbose=False)
-        assert s.ddim_timesteps[0] == 1 and s.ddim_timesteps[-1] == 996
-        # there is no CPU fallback behind the plugin: the forward refuses a CPU tensor loudly
-        with pytest.raises(RuntimeError):
-            ld.model.diffusion_model(torch.zeros(1, 8, 256, 16), torch.zeros(1), context_list=[], context_attn_mask_list=[])
-    finally:
-        rddpm.DDIMSampler = saved
 
 
 class _ReferenceShapedModel:
@@ -135,55 +79,6 @@ def _cond_keys():
     return {a: tuple(b) for a, b in k["hot"].items()}, {a: tuple(b) for a, b in k["cond"].items()}
 
 
-@pytest.mark.skipif(not refimport.available(), reason="needs the reference checkout (build container only)")
-def test_real_reference_latent_diffusion_builds_the_hip_conditioner_stack_from_config_strings():
-    """The reference's LatentDiffusion (ddpm.py:640) + its instantiate_from_config (utils.py:95-114) build OUR conditioners
-    from `cond_stage_config` target strings alone — `SequenceGenAudioMAECond` (the actual target of
-    `crossattn_audiomae_generated`, utils.py:354) over CLAP text + FLAN-T5 + the AudioMAE stand-in, and the outer FLAN-T5 —
-    and their state-dict keys are exactly the ones the real reference classes hold (fixture e2econd_statedict_keys.json,
-    written by oracle/make_golden.py from the REAL SequenceGenAudioMAECond / FlanT5HiddenState)."""
-    refimport.install()
-    import audioldm2.latent_diffusion.models.ddpm as rddpm
-    import audioldm2.utils as ru
-
-    import audioldm2_amd.clap as aclap
-    import audioldm2_amd.seqgen as aseq
-    import audioldm2_amd.t5 as at5
-    from audioldm2_amd.pipeline import hip_cond_stage_config
-    P = ru.default_audioldm_config("audioldm2-full")["model"]["params"]
-    ref_cond = P["cond_stage_config"]
-    ours = hip_cond_stage_config("audioldm2-full", t5_config=cases.t5_test_config(), clap_config=cases.clap_text_test_config())
-    # same keys, same order, same routing keys and the same params for the generator as the reference's own config
-    assert list(ours) == list(ref_cond)
-    for k in ours:
-        assert ours[k]["cond_stage_key"] == ref_cond[k]["cond_stage_key"]
-        assert ours[k]["conditioning_key"] == ref_cond[k]["conditioning_key"]
-    rp, op = ref_cond["crossattn_audiomae_generated"]["params"], ours["crossattn_audiomae_generated"]["params"]
-    assert {k: v for k, v in rp.items() if k != "cond_stage_config"} == {k: v for k, v in op.items() if k != "cond_stage_config"}
-    assert list(rp["cond_stage_config"]) == list(op["cond_stage_config"])
-    P["unet_config"]["target"] = "audioldm2_amd.unet.UNetModel"
-    P["first_stage_config"]["target"] = "audioldm2_amd.vae.AutoencoderKL"
-    P["cond_stage_config"] = ours
-    P["device"] = "cpu"
-    torch.manual_seed(0)
-    ld = rddpm.LatentDiffusion(**P).eval()
-    seq = ld.cond_stage_models[0]
-    assert isinstance(seq, aseq.SequenceGenAudioMAECond) and isinstance(ld.cond_stage_models[1], at5.FlanT5HiddenState)
-    assert isinstance(seq.cond_stage_models[0], aclap.CLAPAudioEmbeddingClassifierFreev2)
-    assert isinstance(seq.cond_stage_models[1], at5.FlanT5HiddenState)
-    assert isinstance(seq.cond_stage_models[2], aseq.AudioMAEConditionCTPoolRand)
-    assert ld.cond_stage_model_metadata["crossattn_audiomae_generated"]["cond_stage_key"] == "all"
-    if os.path.exists(os.path.join(GOLD, "e2econd_statedict_keys.json")):
-        _, cond = _cond_keys()
-        mine = {k: tuple(v.shape) for k, v in ld.state_dict().items() if k.startswith("cond_stage_models.")}
-        missing = [k for k in cond if k not in mine]
-        assert not missing, missing[:5]
-        assert all(mine[k] == cond[k] for k in cond)
-    # the unconditional condition is the reference's dict (encoders/modules.py:265-271); route() takes its LAST crossattn entry
-    # (CPU tensors are fine here: no kernel runs)
-    seq.cond_stage_models[2].get_unconditional_condition(2)
-
-
 @pytest.mark.gpu
 @pytest.mark.skipif(not os.path.exists(os.path.join(GOLD, "e2e_cond_4step_b2.npz")), reason="conditioner e2e fixture absent")
 def test_prompts_to_waveform_through_the_hip_conditioner_stack():
@@ -239,21 +134,14 @@ def test_prompts_to_waveform_through_the_hip_conditioner_stack():
     assert max(eh, ed) < 1e-3 and max(eh, ed) < 1e-3 * float(g["wave_between_rms"])
 
 
-@pytest.mark.skipif(not refimport.available(), reason="needs the reference checkout (build container only)")
 def test_schedule_and_conditioning_helpers_equal_the_reference_methods():
     """q_sample / predict_start_from_noise / q_posterior / get_learned_conditioning / filter_useful_cond_dict of OUR
-    LatentDiffusion against the same methods of the REAL reference class (ddpm.py:357-373, 430-436, 804-828, 958-971) built
-    with the same config: bit-equal (the tables are the same fp32 numbers, the arithmetic the same torch expressions)."""
-    refimport.install()
-    import audioldm2.latent_diffusion.models.ddpm as rddpm
-    import audioldm2.utils as ru
+    LatentDiffusion against what the same methods of the REAL reference class (ddpm.py:357-373, 430-436, 804-828, 958-971), built
+    with the same config, returned on the same inputs (recorded by `oracle/make_golden.py host`): bit-equal (the tables are the
+    same fp32 numbers, the arithmetic the same torch expressions)."""
     from audioldm2_amd import pipeline as P
-    rp = ru.default_audioldm_config("audioldm2-full")["model"]["params"]
-    rp["unet_config"]["target"] = "audioldm2_amd.unet.UNetModel"
-    rp["first_stage_config"]["target"] = "audioldm2_amd.vae.AutoencoderKL"
-    rp["cond_stage_config"] = cases.e2e_cond_config("cpu")
-    rp["device"] = "cpu"
-    ref = rddpm.LatentDiffusion(**rp).eval()
+    ref = np.load(os.path.join(GOLD, "reference_host.npz"))
+    want = lambda k: torch.from_numpy(ref[k])
     op = P.default_audioldm_config("audioldm2-full")["model"]["params"]
     op["cond_stage_config"] = cases.e2e_cond_config("cpu")
     op["device"], op["build_clap"] = "cpu", False
@@ -261,25 +149,27 @@ def test_schedule_and_conditioning_helpers_equal_the_reference_methods():
     g = torch.Generator().manual_seed(0)
     x0, xt, eps = (torch.randn(3, 8, 16, 16, generator=g) for _ in range(3))
     t = torch.tensor([0, 417, 999])
-    assert torch.equal(ours.q_sample(x0, t, eps), ref.q_sample(x0, t, eps))
-    assert torch.equal(ours.predict_start_from_noise(xt, t, eps), ref.predict_start_from_noise(xt, t, eps))
-    for a, b in zip(ours.q_posterior(x0, xt, t), ref.q_posterior(x0, xt, t)):
+    assert torch.equal(ours.q_sample(x0, t, eps), want("q_sample"))
+    assert torch.equal(ours.predict_start_from_noise(xt, t, eps), want("predict_start_from_noise"))
+    for i, a in enumerate(ours.q_posterior(x0, xt, t)):
+        b = want(f"q_posterior{i}")
         assert torch.equal(a.expand_as(b), b)
     torch.manual_seed(7)
-    a = ours.q_sample(x0, t)
-    torch.manual_seed(7)
-    assert torch.equal(a, ref.q_sample(x0, t))                        # the same randn_like draw when no noise is given
+    assert torch.equal(ours.q_sample(x0, t), want("q_sample_drawn"))    # the same randn_like draw when no noise is given
     batch = cases.e2e_batch(2)
-    for key, meta in ref.cond_stage_model_metadata.items():
+    keys = json.loads(str(ref["uncond_keys"]))
+    assert list(ours.cond_stage_model_metadata) == keys
+    for key in keys:
+        meta = ours.cond_stage_model_metadata[key]
         xc = batch if meta["cond_stage_key"] == "all" else batch[meta["cond_stage_key"]]
-        u_ref = ref.get_learned_conditioning(xc, key, unconditional_cfg=True)
         u_our = ours.get_learned_conditioning(xc, key, unconditional_cfg=True)
         flat = lambda v: list(v) if isinstance(v, (list, tuple)) else [v]
-        for p, q in zip(flat(u_our), flat(u_ref)):
-            assert torch.equal(p, q), key
-    d = {k: torch.zeros(1) for k in ref.cond_stage_model_metadata}
+        for j, p in enumerate(flat(u_our)):
+            assert torch.equal(p, want(f"uncond_{key}_{j}")), key
+        assert f"uncond_{key}_{len(flat(u_our))}" not in ref.files, key
+    d = {k: torch.zeros(1) for k in keys}
     d["noise"] = torch.ones(1)
-    assert list(ours.filter_useful_cond_dict(d).keys()) == list(ref.filter_useful_cond_dict(d).keys())
+    assert list(ours.filter_useful_cond_dict(d).keys()) == json.loads(str(ref["filter_useful_keys"]))
     with pytest.raises(AssertionError):
         ours.filter_useful_cond_dict({"noise": d["noise"]})
 
