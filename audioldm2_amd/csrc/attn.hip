@@ -659,7 +659,7 @@ __global__ __launch_bounds__(256) void attention_d32_pipe_kernel(
 //     previous P.V has consumed), K and V^T tiles land in the two register sets their MFMAs read, alternately — the key loop is
 //     unrolled by two on the tile parity;
 //   * tile 0's Q.K^T and softmax run as a prologue instead of a whole iteration multiplying a zero P_{-1}.
-// Only for what the UNet's self-attention launches: K / V^T pre-split by the QKV epilogue, no mask, Lk % 32 == 0.
+// Only for what the UNet's self-attention launches: K / V^T pre-split by the QKV epilogue, no mask, Lk % 32 == 0 (TAIL: any Lk).
 template <int N, int S>
 constexpr int item_slot(int k, int base) { return base + (k * S) / N; }
 
@@ -682,12 +682,19 @@ constexpr int item_slot(int k, int base) { return base + (k * S) / N; }
 #ifndef ALDM_F16_POFF
 #define ALDM_F16_POFF 15.0f   // log2 of the factor the fp16 probabilities carry
 #endif
-template <int QT, int NP, bool LDSKV = false, bool F16 = false>
+// TAIL (v10): Lk need not be a multiple of 32 — the images hold ceil(Lk / 32) key tiles per (sample, head) and the last one is
+// partial.  Its scores of keys >= Lk are -inf before the row max (so neither the max, the F16 form's integer reference nor the
+// sum sees them: exactly the fp32-K/V kernel's ragged-tile mask) and its V^T fragment of those keys is zeroed in registers before
+// the last P.V (aldm_vt_regroup zero-fills that tail; the kernel does not rely on it: 0 x NaN would be NaN).  The K rows of those
+// keys lie past the (sample, head) buffer descriptor's range and load 0 — masked either way.  Compiled only into
+// the ragged instantiations: the aligned ones are unchanged.
+template <int QT, int NP, bool LDSKV = false, bool F16 = false, bool TAIL = false>
 __global__ __launch_bounds__(256) void attention_d32_presplit2_kernel(
     const float* __restrict__ q, const void* __restrict__ k_img, const void* __restrict__ vt_img, float* __restrict__ out,
     int Lq, int Lk, int ldq, int heads, int ldo, float scale, void* __restrict__ out_split, int split_c, int parts,
     float q_mul = 0.f, float sc_c = 1.f, float out_mul = 1.f, float out_img_scale = 0.f) {
     static_assert(!F16 || NP == 2, "fp16 images have two parts");
+    static_assert(!TAIL || !LDSKV, "the LDS-K/V schedule runs whole key tiles only");
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     const int l31 = lane & 31;
@@ -737,14 +744,15 @@ __global__ __launch_bounds__(256) void attention_d32_presplit2_kernel(
 
     // the images of this (sample, head): k rows [key][heads][NP][32] bf16, v tiles [tile][NP][32 dims][32 keys] bf16
     const char* kimg = reinterpret_cast<const char*>(k_img) + ((int64_t)b * Lk * heads + h) * (64 * NP);
-    const char* vimg = reinterpret_cast<const char*>(vt_img) + ((int64_t)b * heads + h) * (Lk >> 5) * (int64_t)(NP * 2048);
+    const char* vimg = reinterpret_cast<const char*>(vt_img) + ((int64_t)b * heads + h) * (TAIL ? (Lk + 31) >> 5 : Lk >> 5) *
+                                                                 (int64_t)(NP * 2048);
     const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<char*>(kimg), 0, ((Lk - 1) * heads + 1) * (64 * NP), 0x00020000);
     const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<char*>(vimg), 0, (Lk >> 5) * NP * 2048, 0x00020000);
+        const_cast<char*>(vimg), 0, (TAIL ? (Lk + 31) >> 5 : Lk >> 5) * NP * 2048, 0x00020000);
     const int koff = l31 * heads * (64 * NP) + lh * 32;
     const int voff = l31 * 64 + lh * 16;
-    const int nt = Lk >> 5;
+    const int nt = TAIL ? (Lk + 31) >> 5 : Lk >> 5;
     const int t_last = nt - 1;    // prefetches past the end re-read the last tile (never used)
 
     u32x4 Kr[2][2][NP], Vr[2][2][NP];   // [tile parity][k-step][part]: the landing registers ARE the MFMA operands
@@ -848,10 +856,17 @@ __global__ __launch_bounds__(256) void attention_d32_presplit2_kernel(
 #pragma unroll
         for (int e = 8 * hh; e < 8 * hh + 8; ++e) oT[t][e] *= alpha[t];
     };
-    // MX: running max of query tile t, first / second 8 scores (+ the cross-half exchange, alpha, m_run)
-    auto item_mx = [&](auto pc, int t, int a) {
+    // MX: running max of query tile t, first / second 8 scores (+ the cross-half exchange, alpha, m_run); `tile` = the scores' tile
+    auto item_mx = [&](auto pc, int t, int a, int tile) {
         constexpr int P = decltype(pc)::value;
         if (a == 0) {
+            if constexpr (TAIL) {
+                if (tile == t_last) {   // (wave uniform) score r of lane half lh is key 32 tile + 4 lh + (r & 3) + 8 (r >> 2)
+                    const int lim = Lk - 32 * tile - 4 * lh;
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) S[P][t][r] = (r & 3) + 8 * (r >> 2) >= lim ? -INFINITY : S[P][t][r];
+                }
+            }
             float mx = S[P][t][0];
 #pragma unroll
             for (int r = 1; r < 8; ++r) mx = fmaxf(mx, S[P][t][r]);
@@ -937,7 +952,7 @@ __global__ __launch_bounds__(256) void attention_d32_presplit2_kernel(
         using QC = std::integral_constant<int, Q>;
         if constexpr (k == 0) load_k(pc, j + 2);   // Kr[P] is free: every Q.K^T MFMA of tile j has been issued and has read it
         else if constexpr (k < 1 + NSP) item_sp(QC{}, (MV + k - 1) / 4, 1, (MV + k - 1) % 4);
-        else if constexpr (k < 1 + NSP + 2 * QT) item_mx(pc, (k - 1 - NSP) / 2, (k - 1 - NSP) % 2);
+        else if constexpr (k < 1 + NSP + 2 * QT) item_mx(pc, (k - 1 - NSP) / 2, (k - 1 - NSP) % 2, j);
         else item_ex(pc, (k - 1 - NSP - 2 * QT) / 4, (k - 1 - NSP - 2 * QT) % 4);
     };
 
@@ -989,8 +1004,8 @@ __global__ __launch_bounds__(256) void attention_d32_presplit2_kernel(
     load_k(P0{}, 2);
 #pragma unroll
     for (int t = 0; t < QT; ++t) {
-        item_mx(P0{}, t, 0);
-        item_mx(P0{}, t, 1);
+        item_mx(P0{}, t, 0, 0);
+        item_mx(P0{}, t, 1, 0);
 #pragma unroll
         for (int g = 0; g < 4; ++g) item_ex(P0{}, t, g);
     }
@@ -1003,6 +1018,7 @@ __global__ __launch_bounds__(256) void attention_d32_presplit2_kernel(
     }
     // the last tile's probabilities: split, rescale, P.V — un-overlapped
     auto tail = [&](auto pc) {   // pc: parity of the LAST tile
+        constexpr int P = decltype(pc)::value;
 #pragma unroll
         for (int t = 0; t < QT; ++t) {
 #pragma unroll
@@ -1011,6 +1027,20 @@ __global__ __launch_bounds__(256) void attention_d32_presplit2_kernel(
                 for (int p = 0; p < 4; ++p) item_sp(pc, t, s, p);
             item_rs(t, 0);
             item_rs(t, 1);
+        }
+        if constexpr (TAIL) {
+            // V^T element e of k-step s, lane half lh is key 16 s + 4 lh + (e & 3) + 8 (e >> 2) of the tile (the P operand's order);
+            // dword w holds elements 2w, 2w + 1
+            const int lim = Lk - 32 * t_last - 4 * lh;
+#pragma unroll
+            for (int s = 0; s < 2; ++s)
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    const int k0 = 16 * s + (2 * w & 3) + 8 * (w >> 1);
+                    const unsigned keep = (k0 < lim ? 0x0000FFFFu : 0u) | (k0 + 1 < lim ? 0xFFFF0000u : 0u);
+#pragma unroll
+                    for (int p = 0; p < NP; ++p) Vr[P][s][p][w] &= keep;
+                }
         }
         static_for<0, NMF>([&](auto ic) { mfma_pv(pc, ic); });
     };
@@ -1441,9 +1471,56 @@ __global__ __launch_bounds__(256) void attention_d32_presplit3_kernel(
 }
 
 
+// ---- ragged token counts (ABI v10) -----------------------------------------------------------------------------------------
+// An ALDM_EPI_QKV launch over M = B L rows with L % 32 != 0 cannot write v^T per (sample, key tile) from a 32-row slab (a slab may
+// straddle two samples); it runs with qkv_rows = M rounded up to 32 instead — ONE padded sample, [head][M / 32 tiles][part][32 dims]
+// [32 keys] — and this kernel regroups that image into the per-(sample, head) one of ceil(L / 32) tiles that
+// attention_d32_presplit2_kernel<..., TAIL> reads, zero-filling the last tile's keys >= L.  In-tile key kk sits at position
+// vt_key_pos(kk) of its dim's 32 keys (bits 2 and 3 swapped: the 32x32 MFMA accumulator row order; the map is its own inverse).
+// One thread per destination dword (two keys of one dim); the GEMM kernels themselves are unchanged.
+__device__ __forceinline__ int vt_key_pos(int kk) { return (kk & 0x13) | ((kk & 4) << 1) | ((kk & 8) >> 1); }
+
+__global__ __launch_bounds__(256) void vt_regroup_kernel(const unsigned short* __restrict__ src, unsigned* __restrict__ dst, int L,
+                                                         int heads, int parts, int tiles, int src_tiles, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    // dst dword i = [b][h][t][p][d][w]: positions 2w, 2w + 1 of dim d
+    const int w = (int)(i & 15), d = (int)((i >> 4) & 31);
+    int64_t r = i >> 9;
+    const int p = (int)(r % parts);
+    r /= parts;
+    const int t = (int)(r % tiles);
+    r /= tiles;
+    const int h = (int)(r % heads);
+    const int64_t b = r / heads;
+    unsigned v = 0u;
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        const int key = 32 * t + vt_key_pos(2 * w + e);
+        if (key < L) {
+            const int64_t m = b * L + key;
+            v |= (unsigned)src[(((int64_t)h * src_tiles + (m >> 5)) * parts + p) * 1024 + d * 32 + vt_key_pos((int)(m & 31))] << (16 * e);
+        }
+    }
+    dst[i] = v;
+}
+
 }  // namespace aldm
 
 using namespace aldm;
+
+extern "C" int aldm_vt_regroup(const void* src, void* dst, int B, int L, int heads, int parts, void* stream) {
+    ALDM_CHECK(src && dst && src != dst, "aldm_vt_regroup: null or aliased pointer");
+    ALDM_CHECK(B > 0 && L > 0 && heads > 0 && (parts == 2 || parts == 3), "aldm_vt_regroup: bad sizes");
+    const int tiles = (L + 31) >> 5;
+    const int src_tiles = (int)(((int64_t)B * L + 31) >> 5);
+    const int64_t n = (int64_t)B * heads * tiles * parts * 512;
+    hipLaunchKernelGGL(vt_regroup_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const unsigned short*>(src), reinterpret_cast<unsigned*>(dst), L, heads, parts, tiles,
+                       src_tiles, n);
+    ALDM_LAUNCH_CHECK("aldm_vt_regroup");
+    return 0;
+}
 
 // matrix-core path of the attention kernel: -1 = default (bf16x3 since round 2: 1024x1024 self-attention 202 us on the
 // fp32 MFMA, 139 us as bf16x6, see profiles/r02_attn_ab*.txt; $ALDM_ATTN_MMA = f32 | bf16x6 | bf16x3 overrides),
@@ -1548,7 +1625,7 @@ extern "C" int aldm_attention_d32_presplit(const float* q, const void* k_split, 
                                            float scale, void* stream) {
     ALDM_CHECK(q && k_split && vt_split && (out || out_split), "aldm_attention_d32_presplit: null pointer");
     ALDM_CHECK(parts == 2 || parts == 3, "aldm_attention_d32_presplit: parts must be 2 or 3");
-    ALDM_CHECK(B > 0 && heads > 0 && Lq > 0 && Lk > 0 && Lk % 32 == 0, "aldm_attention_d32_presplit: Lk must be a multiple of 32");
+    ALDM_CHECK(B > 0 && heads > 0 && Lq > 0 && Lk > 0, "aldm_attention_d32_presplit: bad sizes");
     if (!out) ldo = heads * 32;
     ALDM_CHECK(ldq % 4 == 0 && ldo % 4 == 0 && ldq >= heads * 32 && ldo >= heads * 32,
                "aldm_attention_d32_presplit: row pitches must be multiples of 4 and >= heads*32");
@@ -1581,13 +1658,18 @@ extern "C" int aldm_attention_d32_presplit(const float* q, const void* k_split, 
         return e == nullptr ? 1 : (e[0] == '0' ? 0 : (e[0] == '2' ? 2 : (e[0] == '3' ? 3 : 1)));
     }();
     const int gs = g_attn_sched.load();
-    const int sched = gs < 0 ? env_sched : gs;
+    // a ragged last key tile (Lk % 32 != 0) is handled by the default schedule's TAIL instantiations only
+    const bool ragged = Lk % 32 != 0;
+    const int sched = ragged ? 1 : (gs < 0 ? env_sched : gs);
 #define ALDM_ATTN_PRE(Q_, P_)                                                                                          \
     hipLaunchKernelGGL((attention_d32_pipe_kernel<false, Q_, P_, true>), grid, dim3(256), 0, st, q, kf, vf, out, Lq, Lk, ldq, \
                        heads, 0, ldo, nullptr, scale, out_split, split_c, parts)
 #define ALDM_ATTN_PRE2(K_, Q_, P_)                                                                                     \
     hipLaunchKernelGGL((K_<Q_, P_>), grid, dim3(256), 0, st, q, k_split, vt_split, out, Lq, Lk, ldq, heads, ldo, scale,  \
                        out_split, split_c, parts)
+#define ALDM_ATTN_PRE2T(Q_, P_)                                                                                               \
+    hipLaunchKernelGGL((attention_d32_presplit2_kernel<Q_, P_, false, false, true>), grid, dim3(256), 0, st, q, k_split, vt_split, out, \
+                       Lq, Lk, ldq, heads, ldo, scale, out_split, split_c, parts)
     if (sched == 2) {
         if (parts == 2) {
             if (qt2) ALDM_ATTN_PRE2(attention_d32_presplit3_kernel, 2, 2);
@@ -1609,6 +1691,14 @@ extern "C" int aldm_attention_d32_presplit(const float* q, const void* k_split, 
             else ALDM_ATTN_PRE4(1, 3);
         }
 #undef ALDM_ATTN_PRE4
+    } else if (ragged) {
+        if (parts == 2) {
+            if (qt2) ALDM_ATTN_PRE2T(2, 2);
+            else ALDM_ATTN_PRE2T(1, 2);
+        } else {
+            if (qt2) ALDM_ATTN_PRE2T(2, 3);
+            else ALDM_ATTN_PRE2T(1, 3);
+        }
     } else if (sched == 1 || sched == 3) {
         if (parts == 2) {
             if (qt2) ALDM_ATTN_PRE2(attention_d32_presplit2_kernel, 2, 2);
@@ -1624,6 +1714,7 @@ extern "C" int aldm_attention_d32_presplit(const float* q, const void* k_split, 
         if (qt2) ALDM_ATTN_PRE(2, 3);
         else ALDM_ATTN_PRE(1, 3);
     }
+#undef ALDM_ATTN_PRE2T
 #undef ALDM_ATTN_PRE2
 #undef ALDM_ATTN_PRE
     ALDM_LAUNCH_CHECK("aldm_attention_d32_presplit");
@@ -1643,7 +1734,7 @@ extern "C" int aldm_attention_d32_presplit_f16(const float* q, const void* k_spl
                "aldm_attention_d32_presplit_f16: out_parts must be 2 or 3 (bf16 image) or 0 with out_scale > 0 (fp16 image)");
     const float out_img_scale = out_parts == 0 ? out_scale : 0.f;
     ALDM_CHECK(q_scale > 0.f && k_scale > 0.f && v_scale > 0.f, "aldm_attention_d32_presplit_f16: scales must be positive");
-    ALDM_CHECK(B > 0 && heads > 0 && Lq > 0 && Lk > 0 && Lk % 32 == 0, "aldm_attention_d32_presplit_f16: Lk must be a multiple of 32");
+    ALDM_CHECK(B > 0 && heads > 0 && Lq > 0 && Lk > 0, "aldm_attention_d32_presplit_f16: bad sizes");
     if (!out) ldo = heads * 32;
     ALDM_CHECK(ldq % 4 == 0 && ldo % 4 == 0 && ldq >= heads * 32 && ldo >= heads * 32,
                "aldm_attention_d32_presplit_f16: row pitches must be multiples of 4 and >= heads*32");
@@ -1659,7 +1750,14 @@ extern "C" int aldm_attention_d32_presplit_f16(const float* q, const void* k_spl
     hipStream_t st = (hipStream_t)stream;
     const float q_mul = scale * 1.44269504088896340736f * q_scale, sc_c = 1.0f / (q_scale * k_scale), out_mul = 1.0f / v_scale;
     const int split_c = heads * 32;
-    if (qt2)
+    if (Lk % 32 != 0) {   // ragged last key tile
+        if (qt2)
+            hipLaunchKernelGGL((attention_d32_presplit2_kernel<2, 2, false, true, true>), grid, dim3(256), 0, st, q, k_split, vt_split, out,
+                               Lq, Lk, ldq, heads, ldo, scale, out_split, split_c, out_parts, q_mul, sc_c, out_mul, out_img_scale);
+        else
+            hipLaunchKernelGGL((attention_d32_presplit2_kernel<1, 2, false, true, true>), grid, dim3(256), 0, st, q, k_split, vt_split, out,
+                               Lq, Lk, ldq, heads, ldo, scale, out_split, split_c, out_parts, q_mul, sc_c, out_mul, out_img_scale);
+    } else if (qt2)
         hipLaunchKernelGGL((attention_d32_presplit2_kernel<2, 2, false, true>), grid, dim3(256), 0, st, q, k_split, vt_split, out, Lq, Lk,
                            ldq, heads, ldo, scale, out_split, split_c, out_parts, q_mul, sc_c, out_mul, out_img_scale);
     else

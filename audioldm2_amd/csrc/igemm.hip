@@ -385,11 +385,13 @@ static int igemm_prepare(const aldm_igemm_desc* dd, IgemmK& p, int& BM, int& BN)
     if (qkv) {
         auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
         ALDM_CHECK(d.a_split && d.qkv_c > 0 && d.qkv_c % 64 == 0 && d.N == 3 * d.qkv_c && d.qkv_rows > 0 && d.qkv_rows % 32 == 0 &&
-                       ((int64_t)d.B * d.OH * d.OW) % d.qkv_rows == 0 && d.out && d.k_split && d.vt_split && al16(d.out) &&
+                       (((int64_t)d.B * d.OH * d.OW) % d.qkv_rows == 0 ||
+                        d.qkv_rows == (((int64_t)d.B * d.OH * d.OW + 31) & ~(int64_t)31)) && d.out && d.k_split && d.vt_split && al16(d.out) &&
                        al16(d.k_split) && al16(d.vt_split) && d.ldo >= d.qkv_c && (d.ldo & 3) == 0 && !d.bias && !d.rowbias &&
                        !d.res && !d.out_split && !d.accumulate && d.out_mul == 0 && d.act == ALDM_ACT_NONE && d.alpha == 1.0f &&
                        d.batch <= 1,
-                   "aldm_igemm: ALDM_EPI_QKV needs a pre-split operand, N = 3*qkv_c (qkv_c %% 64 == 0), qkv_rows %% 32 == 0, "
+                   "aldm_igemm: ALDM_EPI_QKV needs a pre-split operand, N = 3*qkv_c (qkv_c %% 64 == 0), qkv_rows %% 32 == 0 dividing M "
+                   "(or M rounded up to 32), "
                    "aligned out / k_split / vt_split and a plain epilogue");
     }
     if (geglu) {

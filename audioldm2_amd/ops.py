@@ -610,13 +610,17 @@ def linear_qkv(x: "SplitT", pw: Packed, heads: int, rows_per_sample: int):
     """The fused self-attention projection [q | k | v] = x W^T (pw: the three weights concatenated along N, no bias) with the
     ALDM_EPI_QKV epilogue: returns (q fp32 [..., C], k_img, vt_img) — k as the split image of its columns, v transposed per
     (sample, head, 32-key tile) straight from the accumulators — the operands ops.attention_presplit multiplies without
-    splitting anything in its key loop.  x: a SplitT [B, L, C_in] (DMA-fed launch)."""
+    splitting anything in its key loop.  x: a SplitT [B, L, C_in] (DMA-fed launch).  Any rows_per_sample L: with L % 32 != 0
+    the projection writes v^T as one padded sample and aldm_vt_regroup splits it into ceil(L / 32) tiles per (sample, head), the
+    last one partial.  (k_img is then allocated with 31 rows past its end, which the attention kernel does not need — its K loads
+    of keys >= L fall outside the buffer descriptor's range and read 0 — so that no 32-key tile read could leave the allocation.)"""
     assert isinstance(x, SplitT) and pw.KH == 1 and pw.KW == 1 and pw.bias is None
     Cq = heads * 32
     assert pw.N == 3 * Cq and x.shape[-1] == pw.Cin
     M = x.rows
-    assert M % rows_per_sample == 0 and rows_per_sample % 32 == 0
+    assert M % rows_per_sample == 0
     Bn = M // rows_per_sample
+    ragged = rows_per_sample % 32 != 0
     # "f16x3": q, k, v of a LayerNorm-fed projection are bounded by R c (R the rows' 2-norm bound, c the weight's largest column
     # norm) — K and V^T are written as fp16 images under that bound and the attention runs three products too; without a bound
     # (or with the switch off) they are 3-part bf16 images and the attention runs bf16x6 behind the f16x3 projection
@@ -624,8 +628,13 @@ def linear_qkv(x: "SplitT", pw: Packed, heads: int, rows_per_sample: int):
     P = 2 if f16_kv else (3 if x.fmt == "f16" else x.parts)
     dev = x.device
     q = torch.empty((*x.shape[:-1], Cq), device=dev, dtype=torch.float32)
-    k_img = torch.empty((M, heads, P, 32), device=dev, dtype=torch.int16)
-    vt_img = torch.empty((Bn, heads, rows_per_sample // 32, P, 32, 32), device=dev, dtype=torch.int16)
+    if ragged:
+        k_img = torch.empty((M + 31, heads, P, 32), device=dev, dtype=torch.int16)[:M]
+        vt_img = torch.empty((Bn, heads, -(-rows_per_sample // 32), P, 32, 32), device=dev, dtype=torch.int16)
+        vt_raw = torch.empty((heads, -(-M // 32), P, 32, 32), device=dev, dtype=torch.int16)
+    else:
+        k_img = torch.empty((M, heads, P, 32), device=dev, dtype=torch.int16)
+        vt_img = torch.empty((Bn, heads, rows_per_sample // 32, P, 32, 32), device=dev, dtype=torch.int16)
     d = IgemmDesc()
     _set_split_operand(d, x, pw)
     d.out_split_parts = P
@@ -641,8 +650,13 @@ def linear_qkv(x: "SplitT", pw: Packed, heads: int, rows_per_sample: int):
     d.w = pw.data.data_ptr(); d.b_mode = B_PACKED; d.K = pw.K; d.N = pw.N
     d.out = q.data_ptr(); d.ldo = Cq; d.alpha = 1.0
     d.k_split = k_img.data_ptr(); d.vt_split = vt_img.data_ptr(); d.qkv_c = Cq; d.qkv_rows = rows_per_sample
+    if ragged:   # one padded sample of M rounded up to 32 rows, regrouped per sample below
+        d.vt_split = vt_raw.data_ptr(); d.qkv_rows = vt_raw.shape[1] * 32
     d.epi_mode = _l.EPI_QKV; d.batch = 1
     _igemm(d, "igemm(qkv)")
+    if ragged:
+        _l.check(_l.load().aldm_vt_regroup(vt_raw.data_ptr(), vt_img.data_ptr(), Bn, rows_per_sample, heads, P, _stream()),
+                 "vt_regroup")
     return q, k_img, vt_img
 
 
@@ -654,7 +668,7 @@ def attention_presplit(q: torch.Tensor, k_img: torch.Tensor, vt_img: torch.Tenso
     B = q.shape[0]
     Lk = k_img.shape[0] // B
     parts = k_img.shape[2]
-    assert q.shape[2] == heads * 32 and k_img.shape[1] == heads and vt_img.shape[0] == B and vt_img.shape[2] * 32 == Lk
+    assert q.shape[2] == heads * 32 and k_img.shape[1] == heads and vt_img.shape[0] == B and vt_img.shape[2] == -(-Lk // 32)
     if scale is None:
         scale = 32 ** -0.5
     out = None if split_out == "only" else torch.empty((B, Lq, heads * 32), device=q.device, dtype=torch.float32)

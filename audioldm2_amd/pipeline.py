@@ -134,6 +134,8 @@ def hip_cond_stage_config(model_name: str = "audioldm2-full", t5_config: Optiona
                            "use_gt_mae_prob": prob, "base_learning_rate": 0.0002, "sequence_gen_length": length,
                            "use_warmup": True, "sequence_input_key": keys, "sequence_input_embed_dim": dims, "batchsize": 16,
                            "cond_stage_config": inner}}
+    if "t5" in model_name:   # utils.py:188-191: the t5 test comes last, it wins over "48k"; utils.py:695-701: FLAN-T5 alone
+        return {"crossattn_flan_t5": copy.deepcopy(t5)}
     if "48k" in model_name:
         return {"film_clap_cond1": copy.deepcopy(clap)}
     if "-speech-" in model_name:
@@ -197,6 +199,21 @@ def default_audioldm_config(model_name: str = "audioldm2-full", t5_len: int = 32
                                     "target": "audioldm2_amd.pipeline.FixedCond",
                                     "params": {"kind": "film", "dim": 512, "seed": 3}}}
         embed_dim = 16
+    if "t5" in model_name:  # utils.py:190-191, 563-706 (audioldm_16k_crossattn_t5): the 16 kHz model, FLAN-T5 cross-attention only
+        unet = {"image_size": 64, "context_dim": [1024], "in_channels": 8, "out_channels": 8,
+                "model_channels": 128, "attention_resolutions": [8, 4, 2], "num_res_blocks": 2,
+                "channel_mult": [1, 2, 3, 5], "num_head_channels": 32, "use_spatial_transformer": True,
+                "transformer_depth": 1}
+        ddconfig = {"double_z": True, "mel_bins": 64, "z_channels": 8, "resolution": 256,
+                    "downsample_time": False, "in_channels": 1, "out_ch": 1, "ch": 128, "ch_mult": [1, 2, 4],
+                    "num_res_blocks": 2, "attn_resolutions": [], "dropout": 0}
+        params.update({"latent_t_size": 256, "latent_f_size": 16, "channels": 8, "sampling_rate": 16000,
+                       "latent_t_per_second": 25.6})
+        t5_cond = {"cond_stage_key": "text", "conditioning_key": "crossattn", "target": "audioldm2_amd.pipeline.FixedCond",
+                   "params": {"kind": "crossattn", "dim": 1024, "length": t5_len, "uncond_length": 1,
+                              "masked_tail": 8 if t5_len > 8 else 0, "seed": 2}}
+        cond = {"crossattn_flan_t5": t5_cond}
+        embed_dim = 8
     if conditioners == "hip":
         cond = hip_cond_stage_config(model_name, t5_config=t5_config, clap_config=clap_config)
         params["build_clap"] = True
@@ -656,6 +673,16 @@ class LatentDiffusion(nn.Module):
             paths.append(path)
         return paths
 
+    @staticmethod
+    def check_latent_t(latent_t):
+        """The UNet halves the latent time axis at three levels and concatenates each up-sampled map with its skip
+        (openaimodel.py:877-880): the reference fails inside that torch.cat unless latent_t is a multiple of 8 (at 100 frames:
+        "Expected size 26 but got size 25").  Say so before any GPU work (10 s at 25.6 or 12.8 latent frames per second:
+        256 / 128; the app's 2.5 s steps: multiples of 64 / 32)."""
+        if isinstance(latent_t, bool) or not isinstance(latent_t, (int, np.integer)) or latent_t <= 0 or latent_t % 8 != 0:
+            raise ValueError(f"latent_t_size must be a positive multiple of 8 (three stride-2 UNet levels), got {latent_t}: "
+                             "pick a duration d with int(d * latent_t_per_second) % 8 == 0")
+
     def _check_candidates(self, n_gen, text=None):
         """Fail BEFORE sampling: n_candidate_gen_per_text > 1 ends in CLAP re-ranking (ddpm.py:1554-1568), which
         needs `self.clap` (a module with cos_similarity(waveform, text)); without it the candidates could only be
@@ -695,6 +722,7 @@ class LatentDiffusion(nn.Module):
         draws the posterior sample (one CPU randn of the latent shape, distributions.py:37-41) only to
         read its batch size; we replay the draw and skip the 345 GFLOP encode."""
         assert x_T is None
+        self.check_latent_t(self.latent_t_size)
         self._check_candidates(n_gen, batch.get("text"))
         use_ddim = ddim_steps is not None
         # DDPM.get_input maps first_stage_key "fbank" to batch["log_mel_spec"] (ddpm.py:482-522)
@@ -781,6 +809,7 @@ class LatentDiffusion(nn.Module):
         self._check_candidates(n_gen, batch.get("text"))
         use_ddim = ddim_steps is not None
         fb = batch["log_mel_spec"] if self.first_stage_key == "fbank" else batch[self.first_stage_key]
+        self.check_latent_t(fb.shape[-2] // 2 ** (self.first_stage_model.encoder.num_resolutions - 1))
         x = fb.unsqueeze(1).float().contiguous().to(self.device)  # DDPM.get_input: [B, 1, T, F]
         z = self.get_first_stage_encoding(self.encode_first_stage(x))  # (R1) posterior draw, really used here
         self._cfg_dropout_draw()                                        # (R1b) every call but the first

@@ -225,10 +225,10 @@ class BasicTransformerBlock(nn.Module):
         so = "only" if (ops.use_dma() and C % 32 == 0) else None
         n = ops.layernorm(h, *pk["ln"][0], split_out=so)
         # self-attention over operands the projection's epilogue pre-splits (round 3): k as a split image, v transposed per key
-        # tile — when the token count is a whole number of 32-key tiles (every UNet level of every config)
-        # (... and the width is a whole number of 64-column tiles — an even head count — and the projection has no bias: what
+        # tile — at any token count (a partial last key tile since ABI v10: the durations other than 10 s)
+        # (... when the width is a whole number of 64-column tiles — an even head count — and the projection has no bias: what
         # ALDM_EPI_QKV requires; anything else takes the fp32 K / V path)
-        pre = so is not None and PRESPLIT_ATTENTION and h.shape[1] % 32 == 0 and C % 64 == 0 and pk["qkv1"].bias is None
+        pre = so is not None and PRESPLIT_ATTENTION and C % 64 == 0 and pk["qkv1"].bias is None
         if pre:
             q, kimg, vtimg = ops.linear_qkv(n, pk["qkv1"], self.heads, h.shape[1])
             a = ops.attention_presplit(q, kimg, vtimg, self.heads, split_out=so)

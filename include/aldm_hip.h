@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 /* ---- library / error ------------------------------------------------------------------ */
-int aldm_version(void);              /* ABI version (9), bumped on any struct / entry change */
+int aldm_version(void);              /* ABI version (10), bumped on any struct / entry change */
 const char* aldm_last_error(void);   /* message of the last failing call on this thread     */
 
 /* ---- activations usable as prologue (applied to the gathered input) or epilogue -------- */
@@ -59,7 +59,9 @@ enum {
  *                            layout (no LDS transposition): [b][head][tile][part][32 dims][32 keys] bf16, the keys of a tile in
  *                            the order the attention kernel's P^T operand holds them (chunk 2s + lh = accumulator registers 8s ..
  *                            8s + 7 of lane half lh, i.e. tile rows (r & 3) + 8 (r >> 2) + 4 lh).
- * Requires C % 32 == 0, the block tile's width dividing C, qkv_rows (rows per sample) % 32 == 0, no split-K.  The split is the
+ * Requires C % 32 == 0, the block tile's width dividing C, qkv_rows (rows per sample) % 32 == 0 dividing M, no split-K.  ABI v10:
+ * qkv_rows may also be M rounded up to 32 — one padded sample, the form a token count L % 32 != 0 takes (a 32-row slab would
+ * straddle two samples): aldm_vt_regroup then turns that v^T image into the per-sample one of ceil(L / 32) tiles.  The split is the
  * one aldm_attention_d32 applies to fp32 K / V in registers (split_parts = 2: (hi, mid) round to nearest; 3: exact), so
  * aldm_attention_d32_presplit over these images gives bit-identical results with ~30 % fewer VALU instructions per key tile. */
 enum { ALDM_EPI_PLAIN = 0, ALDM_EPI_GEGLU = 1, ALDM_EPI_QKV = 2 };
@@ -337,10 +339,17 @@ int aldm_attention_d32_split(const float* q, const float* k, const float* v, flo
                              int parts, int B, int heads, int Lq, int Lk, int ldq, int ldk, int ldv, int ldo,
                              const float* mask, float scale, void* stream);
 /* Self-attention over the pre-split K / V^T images an ALDM_EPI_QKV launch wrote (ABI v6): q fp32 [B, Lq, *] (row pitch ldq),
- * k_split / vt_split as described at ALDM_EPI_QKV with `parts` parts, Lk % 32 == 0, no mask; out / out_split as
- * aldm_attention_d32_split.  `parts` must match the attention mode in force (2 for bf16x3, 3 for bf16x6).              */
+ * k_split / vt_split as described at ALDM_EPI_QKV with `parts` parts, no mask; out / out_split as aldm_attention_d32_split.
+ * Any Lk (ABI v10): with Lk % 32 != 0 the last key tile is partial — its keys >= Lk are masked (their k_split rows lie outside
+ * the (sample, head) buffer descriptor and read as 0: no rows past the image are needed) and schedule 1 runs
+ * whatever aldm_attention_sched says; the same holds for aldm_attention_d32_presplit_f16.  `parts` must match the attention
+ * mode in force (2 for bf16x3, 3 for bf16x6).                                                                            */
 int aldm_attention_d32_presplit(const float* q, const void* k_split, const void* vt_split, float* out, void* out_split,
                                 int parts, int B, int heads, int Lq, int Lk, int ldq, int ldo, float scale, void* stream);
+/* Ragged token counts (ABI v10): src = the v^T image of an ALDM_EPI_QKV launch over B * L rows with qkv_rows = B * L rounded up
+ * to 32 ([heads][ceil(B L / 32)][parts][32][32] bf16 / fp16); dst = the per-sample image [B][heads][ceil(L / 32)][parts][32][32]
+ * aldm_attention_d32_presplit{,_f16} reads, the last tile's keys >= L zero.                                                  */
+int aldm_vt_regroup(const void* src, void* dst, int B, int L, int heads, int parts, void* stream);
 /* Matrix-core path of aldm_attention_d32, PROCESS wide: 1 = fp32 MFMA, 2 = "bf16x6" (both products as 6 bf16 partial
  * products of exact 3-part operand splits), 3 = "bf16x3" ((hi, mid) rounded to nearest, 3 partial products), -1 =
  * default: $ALDM_ATTN_MMA if set, else the engine's $ALDM_MMA, else bf16x6 ("f32" | "bf16x6" | "bf16x3"; anything else is
