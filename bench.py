@@ -14,10 +14,14 @@ metric = audio-seconds / second (whole job, all GPUs).  Weak scaling: per-GPU ba
   python bench.py ... --dump-outputs DIR                (also writes the last timed job's waveform as DIR/waveform.npy: the
                                                         inputs are seeded, so two builds run with the same arguments compare
                                                         output for output)
+  python bench.py ... --full                            (also measures every sub-record listed below, several minutes more)
 
 The headline runs in the library's DEFAULT product mode, "bf16x6": fp32 storage / accumulation, every product evaluated as 6 bf16
 MFMA partial products of exact 3-part operand splits — fp32-grade (2.4e-7 rms per contraction; the fp32 MFMA itself: 2.1e-7), i.e.
-not narrower than the reference's fp32 multiply.  Prints ONE JSON line on rank 0 with the contract keys plus
+not narrower than the reference's fp32 multiply.  Prints ONE JSON line on rank 0 with the contract keys.  A plain run does nothing
+else: set-up, warm-up, the timed jobs, --dump-outputs, the line.  With --full (each leg can still be left out with its --no-* option)
+the line also carries
+  `unet_step_ms`  ms per DDIM step (graph-replayed, its own 20-step sampling run) and its TFLOP/s against the mode's peak;
   `roofline`      dominant igemm instantiation + the attention kernel, measured live with events on the launch stream (the cost of
                   an empty event pair, measured in the same run, is subtracted so the durations compare with rocprofv3's), HBM
                   traffic from profiles/r06_pmc_traffic_<mode>.json while its source hash matches the running kernels;
@@ -121,6 +125,10 @@ def parse():
     ap.add_argument("--model", default="audioldm2-full")
     ap.add_argument("--mma", choices=["bf16x6", "bf16x3", "f32", "f16x3"], default=None,
                     help="matrix-core path of the igemm engine (default: $ALDM_MMA or the library default)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the sub-records (step probe, rooflines, other modes and configurations, "
+                         "conditioners, the API default, replicas, CPU baseline); without it a run measures the headline only")
+    # the --no-* and *-steps options below shape the legs of --full and do nothing without it
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-step-probe", action="store_true")
@@ -652,6 +660,14 @@ def main():
         dst[f"unet_step_frac_of_{mode}_peak"] = round(dst["unet_step_tflops"] / MODE_PEAK[mode], 4)
         dst["unet_step_peak_tflops"] = MODE_PEAK[mode]
 
+    def finish(out):
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            torch.distributed.barrier()
+            torch.distributed.destroy_process_group()
+
+    out = None
     if rank == 0:
         mode = aops.MMA_MODE
         value = gB * audio_seconds * args.steps / dt
@@ -674,6 +690,10 @@ def main():
             out["config"]["dist_world_size"] = torch.distributed.get_world_size()
             out["per_rank_seconds"] = per_rank
             out["rank_skew_pct"] = round(100.0 * (max(per_rank) - min(per_rank)) / max(per_rank), 2)
+    if not args.full:   # a plain run: the headline line and nothing else
+        return finish(out)
+    # ---- --full: the sub-records, measured after the headline; they add keys to the line and change none of the above
+    if rank == 0:
         try:
             if args.no_step_probe:
                 raise RuntimeError("skipped (--no-step-probe)")
@@ -848,9 +868,9 @@ def main():
             import subprocess
             env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
             env["ALDM_DIST_BACKEND"] = "gloo"
+            # a plain run (no --full): the headline job and nothing else
             cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "2", "--steps", "1", "--warmup", "1", "--batch", str(B),
-                   "--ddim-steps", str(args.ddim_steps), "--no-cpu-baseline", "--no-roofline", "--no-step-probe", "--no-fast", "--no-f16x3", "--no-configs",
-                   "--no-conditioners", "--no-api-default", "--no-replicas"] + (["--mma", args.mma] if args.mma else [])
+                   "--ddim-steps", str(args.ddim_steps)] + (["--mma", args.mma] if args.mma else [])
             r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
             line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
             rec = json.loads(line[-1]) if r.returncode == 0 and line else None
@@ -871,10 +891,7 @@ def main():
                 out["cpu_baseline"] = cpu_baseline(1, args.cpu_ddim_steps, args.ddim_steps)
             except Exception as e:  # pragma: no cover - never lose the measured line to the baseline leg
                 out["cpu_baseline"] = {"error": repr(e)}
-        print(json.dumps(out), flush=True)
-    if world > 1:
-        torch.distributed.barrier()
-        torch.distributed.destroy_process_group()
+    finish(out)
 
 
 if __name__ == "__main__":

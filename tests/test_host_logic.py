@@ -221,6 +221,27 @@ def test_bench_contract_defaults_and_no_cpu_path():
         assert r.returncode != 0 and "needs the MI355X" in r.stderr and not r.stdout.strip()
 
 
+def test_bench_sub_records_are_opt_in():
+    """bench.py: a plain run measures the headline alone; the sub-records (step probe, rooflines, other modes and configurations,
+    conditioners, API default, replicas, CPU baseline) come with --full, which is off by default and leaves the headline flags
+    as they are."""
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    old = sys.argv
+    try:
+        sys.argv = ["bench.py"]
+        plain = bench.parse()
+        sys.argv = ["bench.py", "--full", "--no-replicas"]
+        full = bench.parse()
+    finally:
+        sys.argv = old
+    assert plain.full is False and full.full is True and full.no_replicas
+    same = ("gpus", "steps", "warmup", "batch", "ddim_steps", "model", "mma", "dump_outputs")
+    assert [getattr(plain, k) for k in same] == [getattr(full, k) for k in same]
+
+
 @pytest.mark.timeout(600)
 def test_bench_launches_its_own_ranks():
     """`python bench.py --gpus N` (N > 1, no WORLD_SIZE in the environment) re-launches itself under torch.distributed.run with

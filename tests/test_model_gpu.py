@@ -849,3 +849,27 @@ def test_ddim_sampling_timesteps_subset_continues_a_full_run(ld):
     enc = s.stochastic_encode(x0, t, noise=nz)
     want = float(s.ddim_alphas[3]) ** 0.5 * x0.cpu() + float(s.ddim_sqrt_one_minus_alphas[3]) * nz
     assert rel(enc.cpu(), want) < 1e-6
+
+
+@pytest.mark.timeout(600)
+def test_bench_plain_run_prints_the_headline_only(tmp_path):
+    """`bench.py` without --full: set-up, warm-up, the timed jobs, --dump-outputs and ONE JSON line with the contract keys — none
+    of the sub-records that --full measures (a short job: 2 DDIM steps)."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "1", "--ddim-steps", "2",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=500, env=env, cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    rec = json.loads(lines[0])
+    assert rec["metric"] == "audio_seconds_per_second" and rec["unit"] == "audio-s/s" and rec["higher_is_better"] is True
+    assert rec["value"] > 0 and rec["ms_per_step"] > 0 and (rec["steps"], rec["warmup"], rec["n_gpus"]) == (1, 1, 1)
+    assert isinstance(rec["dtype"], str) and rec["dtype"]
+    full_only = {"unet_step_ms", "roofline", "roofline_tail", "fast", "f16x3", "configs", "conditioners", "api_default",
+                 "replicas_one_gpu", "cpu_baseline"}
+    assert not full_only & set(rec), sorted(full_only & set(rec))
+    wav = np.load(tmp_path / "waveform.npy")
+    assert wav.shape == (8, 1, 163872) and np.isfinite(wav).all()

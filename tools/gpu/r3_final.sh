@@ -17,7 +17,7 @@ ALDM_NO_GRAPH=1 timeout 400 rocprofv3 --kernel-trace --pmc WRITE_SIZE --kernel-i
 cd $R
 python tools/pmc_traffic.py /tmp/pmc_fetch /tmp/pmc_write $O/pmc_traffic.json > $O/pmc_traffic.log 2>&1; tail -3 $O/pmc_traffic.log
 cp $O/pmc_traffic.json profiles/r03_pmc_traffic.json
-timeout 900 python bench.py > $O/bench_final.json 2> $O/bench_final.err; tail -2 $O/bench_final.err; cut -c1-3000 $O/bench_final.json
+timeout 900 python bench.py --full > $O/bench_final.json 2> $O/bench_final.err; tail -2 $O/bench_final.err; cut -c1-3000 $O/bench_final.json
 cd /tmp
 timeout 400 rocprofv3 --kernel-trace --stats -d /tmp/prof_fin -o fin --output-format csv -- python $R/bench.py --steps 1 --warmup 0 --ddim-steps 10 --no-cpu-baseline --no-roofline --no-step-probe --no-strict --no-configs > /dev/null 2>&1
 cd $R

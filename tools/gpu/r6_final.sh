@@ -15,7 +15,7 @@ ALDM_NO_GRAPH=1 timeout -k 5 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --ker
 ( cd $R && timeout -k 5 90 python tools/pmc_traffic.py /tmp/pmc_fetch_$MODE /tmp/pmc_write_$MODE $O/pmc_traffic_$MODE.json "ALDM_NO_GRAPH=1 python tools/pmc_unet_pass.py $MODE (two eager UNet passes, batch 8 x CFG)" < /dev/null > $O/pmc_traffic_$MODE.log 2>&1; tail -2 $O/pmc_traffic_$MODE.log; cp $O/pmc_traffic_$MODE.json profiles/r06_pmc_traffic_$MODE.json )
 done
 cd $R
-( time timeout -k 5 1200 python3 bench.py --gpus 1 --steps 20 --warmup 5 < /dev/null ) > $O/bench_final.json 2> $O/bench_final.err; echo "bench rc=$?"; tail -4 $O/bench_final.err; cut -c1-1500 $O/bench_final.json
+( time timeout -k 5 1200 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full < /dev/null ) > $O/bench_final.json 2> $O/bench_final.err; echo "bench rc=$?"; tail -4 $O/bench_final.err; cut -c1-1500 $O/bench_final.json
 for MODE in bf16x6 f16x3; do
 cd /tmp
 rm -rf /tmp/prof_$MODE /tmp/kt_$MODE

@@ -19,7 +19,7 @@ ALDM_MMA=bf16x3 DMA_TUNE_ONLY_HALO=1 DMA_TUNE_MERGE=$O/dma2_merged.json DMA_TUNE
 cp $O/dma2_merged_halo.json audioldm2_amd/tuning/mi355x_igemm_dma_bf16x3.json
 rm -f $O/err_log.tsv
 ALDM_ERR_LOG=$O/err_log.tsv timeout 2400 python -m pytest tests/test_model_gpu.py tests/test_parity_configs_gpu.py tests/test_f16x3_gpu.py -q -m gpu -p no:cacheprovider -k "bf16x3 or f16x3" 2>&1 | tail -4 | tee $O/tests_2part_modes.txt
-Q="--steps 1 --warmup 1 --no-cpu-baseline --no-roofline --no-fast --no-f16x3 --no-configs --no-conditioners --no-api-default --no-replicas"
+Q="--full --steps 1 --warmup 1 --no-cpu-baseline --no-roofline --no-fast --no-f16x3 --no-configs --no-conditioners --no-api-default --no-replicas"
 for M in audioldm2-full audioldm_48k audioldm2-full-large-1150k audioldm2-speech-gigaspeech; do
 for MODE in bf16x6 f16x3; do
 timeout 600 python bench.py --model $M --mma $MODE $Q 2>/dev/null | python -c "

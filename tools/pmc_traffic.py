@@ -36,7 +36,7 @@ def main():
     out = {"source_hash": source_hash(), "igemm_source_hash": source_hash("igemm"), "tuning_hash": tuning_hash(),
            "source": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (two runs) of " +
                      (sys.argv[4] if len(sys.argv) > 4 else
-                      "ALDM_NO_GRAPH=1 python bench.py --steps 1 --warmup 0 --ddim-steps 2 --no-cpu-baseline"),
+                      "ALDM_NO_GRAPH=1 python bench.py --full --steps 1 --warmup 0 --ddim-steps 2 --no-cpu-baseline"),
            "units": "bytes per launch, averaged over all launches of the instantiation in that command (all prologue modes)",
            "kernels": {}}
     for k in sorted(fetch):
