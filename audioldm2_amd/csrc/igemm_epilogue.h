@@ -90,13 +90,17 @@ __device__ __forceinline__ void split4_parts(const f32x4 v, u32x2 (&part)[3], in
 // hi = RN_f16(s x), lo = RN_f16(s x - hi) — 22 of the 24 significand bits while lo is a normal fp16, and an absolute error of at
 // most 2^-25 / s below that (the matrix core honours fp16 subnormals: profiles/r06_f16x3_accuracy.txt).  The producer's s puts
 // |s x| under 65504 by construction (a GroupNorm / LayerNorm output cannot exceed sqrt(n) max|gamma| + max|beta|); the clamp is a
-// seat belt that never engages inside that bound.
+// seat belt that never engages inside that bound.  A NaN goes through as a NaN (fmaxf / fminf return their OTHER argument for
+// one: the bare clamp would turn it into -65504, a finite wrong value where every other mode reports the NaN).
 using f16x4 = _Float16 __attribute__((ext_vector_type(4)));
 using f16x8 = _Float16 __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ void split4_f16(const f32x4 v, float s, u32x2 (&part)[3]) {
     f32x4 x;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) x[e] = __builtin_fminf(__builtin_fmaxf(v[e] * s, -65504.0f), 65504.0f);
+    for (int e = 0; e < 4; ++e) {
+        const float t = v[e] * s;
+        x[e] = t != t ? t : __builtin_fminf(__builtin_fmaxf(t, -65504.0f), 65504.0f);
+    }
     const f16x4 h = __builtin_convertvector(x, f16x4);
     const f16x4 l = __builtin_convertvector(x - __builtin_convertvector(h, f32x4), f16x4);
     part[0] = __builtin_bit_cast(u32x2, h);

@@ -87,6 +87,21 @@ F16_ATTN = os.environ.get("ALDM_F16_ATTN", "1") != "0"       # A/B switch: self-
 F16_ATTN_OUT = os.environ.get("ALDM_F16_ATTN_OUT", "1") != "0"   # A/B switch: that attention's output as an fp16 image (to_out in f16x3)
 
 
+# The guard of the GEGLU fp16 image (Packed.geglu_bound).  One power-of-two scale s serves the whole tensor, 2^14 < s * bound <=
+# 2^15, and an image element is hi + lo with lo rounded to fp16: once lo is subnormal its error is ABSOLUTE, up to 2^-25 in scaled
+# units.  An element 2^-k under the bound is >= 2^(14-k) in scaled units, so it keeps 39 - k to 40 - k significand bits: relative
+# error <= 2^(k-39).  The FF-out contraction sums such elements with independent errors, so its max-norm error relative to the
+# outputs THEY feed is about that of the typical element: the format model (tools/f16x3_outlier_emulation.py) gives 0.4 .. 0.6 x
+# 2^(k-39), k = log2(bound / typical) as geglu_bound estimates it — 6.1e-7 at k = 19.0, 3.4e-5 at k = 25.5 (one gate row x 2^8
+# under the former (R c + b)^2 of the joint column norm), 1.0e-2 at k = 33.5; profiles/r07_f16x3_outlier_errors.txt has the
+# kernels' own numbers.  The fp32-grade bar behind a fused activation is 5e-6 = 2^-17.6 (tests/tolerances.py).  The image is taken
+# while k <= 20: at most 2^-19 = 1.9e-6 by the rule, ~1e-6 by the model, a factor 2.5 .. 5 under the bar for the kernels' fp32
+# accumulation and for the estimate of "typical" (half of the elements are smaller).  Random-init parameters sit at k = 10 .. 13
+# (K = 256 .. 640: the bound's sqrt(K) per factor over a random orientation, and max|gamma| / rms gamma); beyond 20 this launch
+# writes the exact 3-part bf16 image and its consumer runs six products.  Decided from parameters, before any graph capture.
+F16_GEGLU_MAX_SLACK_LOG2 = 20.0
+
+
 def _pow2_scale(bound: float) -> float:
     """The largest power of two s with s * bound <= 32768 (a factor two under fp16's 65504: the bound is mathematical, the slack
     covers fp32 rounding of the normalisation itself)."""
@@ -129,6 +144,23 @@ def _row_norm_bound(gamma: torch.Tensor, beta: Optional[torch.Tensor], C: int) -
     return _absmax_cached(gamma) * math.sqrt(float(C)) + b2
 
 
+def _row_norm_typical(gamma: torch.Tensor, beta: Optional[torch.Tensor]) -> float:
+    """E ||gamma * x_hat + beta||_2^2 = ||gamma||_2^2 + ||beta||_2^2 for a LayerNorm row (x_hat: zero mean, unit variance per
+    element): the size a row HAS, next to the size _row_norm_bound says it cannot exceed.  Parameters only, cached like the bound."""
+    import math
+    c = getattr(gamma, "_aldm_norm2", None)
+    if c is None or c[0] != gamma._version:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("f16x3: the norm of a normalisation's parameters must be known before graph capture (run one eager step)")
+        c = (gamma._version, float(gamma.detach().double().norm()))
+        try:
+            gamma._aldm_norm2 = c
+        except (AttributeError, RuntimeError):
+            pass
+    b2 = 0.0 if beta is None else getattr(beta, "_aldm_norm2", (0, 0.0))[1]   # (_row_norm_bound has just cached it)
+    return math.sqrt(c[1] ** 2 + b2 ** 2)
+
+
 def _norm_f16_scale(gamma: torch.Tensor, beta: Optional[torch.Tensor], n: int) -> float:
     """fp16 image scale of a GroupNorm / LayerNorm output normalised over n elements: |gamma x_hat + beta| <= sqrt(n) max|gamma| +
     max|beta| (|x_hat| <= sqrt(n) holds for any data; SiLU only shrinks)."""
@@ -152,6 +184,8 @@ class Packed:
     w_scale: float = 0.0                    # ... its power-of-two scale
     cmax: Optional[float] = None            # largest column 2-norm (out_bound)
     bmax: float = 0.0
+    geglu: bool = False                     # pack_geglu's order: 32 value columns, their 32 gate columns, ...
+    halves: Optional[tuple] = None          # per half (value, gate): (largest, median column norm, max|b|, rms b) (geglu_bound)
 
     @property
     def K(self) -> int:
@@ -167,6 +201,30 @@ class Packed:
             self.cmax = float(self.data.view(-1, npad, 4).double().pow(2).sum((0, 2)).max().sqrt())
             self.bmax = 0.0 if self.bias is None else float(self.bias.abs().max())
         return rn * self.cmax + self.bmax
+
+    def geglu_bound(self, rn: float, rt: float) -> Tuple[float, float]:
+        """(bound, typical magnitude) of the GEGLU output value * gelu(gate) for LayerNorm rows with ||x||_2 <= rn, typically rt.
+        bound: |value| |gelu(gate)| <= |value| |gate| <= (rn c_v + b_v)(rn c_g + b_g), the two halves of the packed weight with
+        their OWN largest column norm and bias (not the joint maximum squared: one outlier row then widens one factor, not
+        both).  typical: a row of norm rt meets a column of norm m at random orientation, |x . w| ~ rt m / sqrt(K) (Cauchy-
+        Schwarz is sqrt(K) loose there), m the MEDIAN column norm of the half (an outlier row does not move it), plus the rms
+        bias.  Parameters only; read once (host sync, before graph capture) and cached."""
+        import math
+        assert self.geglu
+        if self.halves is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("f16x3: a weight's column norms must be known before graph capture (run one eager step)")
+            npad = self.data.numel() // (4 * ((self.K + 3) // 4))
+            cn = self.data.view(-1, npad, 4).double().pow(2).sum((0, 2)).sqrt()[:self.N].view(-1, 2, 32)
+            b = torch.zeros(self.N, device=self.data.device) if self.bias is None else self.bias
+            b = b.double().view(-1, 2, 32)
+            self.halves = tuple((float(cn[:, j].max()), float(cn[:, j].median()), float(b[:, j].abs().max()),
+                                 float(b[:, j].pow(2).mean().sqrt())) for j in range(2))
+        bound, typ = 1.0, 1.0
+        for cmax, cmed, bmax, brms in self.halves:
+            bound *= rn * cmax + bmax
+            typ *= math.sqrt(rt * rt * cmed * cmed / self.K + brms * brms)
+        return bound, typ
 
     def split16_ptr(self) -> int:
         """Device pointer of the "f16x3" weight image (built on first use, before any graph capture): hi / lo fp16 of w_scale * w,
@@ -209,15 +267,17 @@ class Packed:
 class SplitT:
     """A split image (include/aldm_hip.h "split images"): the exact 3-way bf16 split of a channels-last fp32 tensor of
     logical shape `shape` = [..., C], stored [rows, C/32, 3, 32] as int16 — the pre-split A operand of the DMA-fed GEMM."""
-    __slots__ = ("data", "shape", "fmt", "scale", "rn")
+    __slots__ = ("data", "shape", "fmt", "scale", "rn", "rt")
 
-    def __init__(self, data: torch.Tensor, shape, fmt: str = "bf16", scale: float = 1.0, rn: float = 0.0):
+    def __init__(self, data: torch.Tensor, shape, fmt: str = "bf16", scale: float = 1.0, rn: float = 0.0, rt: float = 0.0):
         self.data = data
         self.shape = tuple(shape)
         self.fmt = fmt        # "bf16" | "f16" (the "f16x3" image: 2 parts, IEEE fp16, of scale * value)
         self.scale = scale
         self.rn = rn          # a-priori bound of a ROW's 2-norm (LayerNorm outputs: sqrt(C) max|gamma| + ||beta||), 0 = unknown:
                               # with it a projection's outputs are bounded by rn * (largest column norm of W) + max|bias|
+        self.rt = rt          # the TYPICAL 2-norm of such a row, sqrt(||gamma||^2 + ||beta||^2) (_row_norm_typical): what the
+                              # fp16-image guard of linear_geglu measures the bound against
 
     @property
     def parts(self) -> int:
@@ -257,7 +317,7 @@ class SplitT:
         tot = self.rows * self.C
         shape = tuple(tot // n if s_ == -1 else s_ for s_ in shape)
         assert shape[-1] == self.C, "a split image can only be re-viewed over its row dimensions"
-        return SplitT(self.data, shape, self.fmt, self.scale, self.rn)
+        return SplitT(self.data, shape, self.fmt, self.scale, self.rn, self.rt)
 
     def float(self) -> torch.Tensor:
         """hi + mid + lo back to fp32 (tests / debugging): exact for bf16 images; (hi + lo) / scale for an fp16 image."""
@@ -560,7 +620,9 @@ def pack_geglu(weight: torch.Tensor, bias: Optional[torch.Tensor]) -> Packed:
     j = torch.arange(2).view(1, -1, 1)
     l = torch.arange(32).view(1, 1, -1)
     perm = (j * inner + g * 32 + l).reshape(-1).to(weight.device)
-    return pack_conv(weight.detach()[perm], None if bias is None else bias.detach()[perm])
+    pw = pack_conv(weight.detach()[perm], None if bias is None else bias.detach()[perm])
+    pw.geglu = True
+    return pw
 
 
 def linear_geglu(x, pw: Packed, split_out: Optional[str] = None, gate_act: int = ACT_NONE):
@@ -578,10 +640,15 @@ def linear_geglu(x, pw: Packed, split_out: Optional[str] = None, gate_act: int =
     so = None
     if split_out:
         if is_split and x.fmt == "f16" and x.rn > 0.0 and f16_mode() and F16_FF_OUT:
-            # "f16x3" all the way through the MLP: |value * gelu(gate)| <= |value| |gate| <= (rn c + b)^2 — the GEGLU output has an
-            # a-priori bound too, so it is written as an fp16 image and the FF-out GEMM runs three products as well
-            so = SplitT.empty(oshape, x.device, f16_scale=_pow2_scale(pw.out_bound(x.rn) ** 2))
-        else:
+            # "f16x3" all the way through the MLP: |value * gelu(gate)| <= |value| |gate| <= (rn c_v + b_v)(rn c_g + b_g) — the GEGLU
+            # output has an a-priori bound too, so it is written as an fp16 image and the FF-out GEMM runs three products as well
+            if pw.geglu:
+                bound, typ = pw.geglu_bound(x.rn, x.rt)
+            else:   # (a weight not packed by pack_geglu: no halves to tell apart)
+                bound, typ = pw.out_bound(x.rn) ** 2, 0.0
+            if typ <= 0.0 or bound <= typ * 2.0 ** F16_GEGLU_MAX_SLACK_LOG2:
+                so = SplitT.empty(oshape, x.device, f16_scale=_pow2_scale(bound))
+        if so is None:   # no bound, or one too far above the data (the guard above): the exact 3-part bf16 image, six products
             so = SplitT.empty(oshape, x.device)
     d = IgemmDesc()
     if is_split:
@@ -643,7 +710,9 @@ def linear_qkv(x: "SplitT", pw: Packed, heads: int, rows_per_sample: int):
         kv_scale = _pow2_scale(bound)
         q_scale = _pow2_scale(bound * (32 ** -0.5) * 1.4426950408889634)
         d.out_split_fmt = _l.FMT_F16; d.out_split_scale = kv_scale; d.vt_scale = kv_scale
-        k_img._aldm_f16 = (q_scale, kv_scale, kv_scale)
+        # (the scales travel as an attribute of BOTH images: a view or a clone of one drops it, and attention_presplit then
+        # finds it on the other — or, with neither, refuses the 2-part image instead of reading fp16 bits as bf16)
+        k_img._aldm_f16 = vt_img._aldm_f16 = (q_scale, kv_scale, kv_scale)
     d.C1 = pw.Cin; d.B = 1; d.H = 1; d.W = M; d.up_h = d.up_w = 1
     d.KH = d.KW = d.SH = d.SW = d.DH = d.DW = 1
     d.OH = 1; d.OW = M
@@ -672,7 +741,11 @@ def attention_presplit(q: torch.Tensor, k_img: torch.Tensor, vt_img: torch.Tenso
     if scale is None:
         scale = 32 ** -0.5
     out = None if split_out == "only" else torch.empty((B, Lq, heads * 32), device=q.device, dtype=torch.float32)
-    f16s = getattr(k_img, "_aldm_f16", None)
+    f16s = getattr(k_img, "_aldm_f16", None) or getattr(vt_img, "_aldm_f16", None)
+    if f16s is None and parts == 2 and f16_mode():
+        # "f16x3" writes 3-part bf16 images or 2-part fp16 ones, never 2-part bf16: this is an fp16 image that lost its scales
+        raise RuntimeError("attention_presplit: a 2-part K / V^T image without its fp16 scales in f16x3 mode (the scales are an "
+                           "attribute of the tensors linear_qkv returned: pass those, not a view or a clone of them)")
     # fp16 K / V^T images: the output is a convex combination of the values (|out| <= max|v|), so its image can be an fp16 one
     # under V's scale and the to_out projection runs three products too (ALDM_F16_ATTN_OUT=0: a 3-part bf16 image, six products)
     f16_out = f16s is not None and F16_ATTN_OUT
@@ -953,6 +1026,7 @@ def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: flo
     if f16_mode():
         so = SplitT.empty(x.shape, x.device, f16_scale=_norm_f16_scale(gamma, beta, Cc))
         so.rn = _row_norm_bound(gamma, beta, Cc)
+        so.rt = _row_norm_typical(gamma, beta)
         _l.check(_l.load().aldm_layernorm_split_f16(x.data_ptr(), _p(y), so.data_ptr(), M, Cc, gamma.data_ptr(), beta.data_ptr(), eps,
                                                     so.scale, _stream()), "layernorm_split_f16")
         return so if split_out == "only" else (y, so)

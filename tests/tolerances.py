@@ -13,6 +13,17 @@ operand significands, which keeps its own (looser) bars.
   VAE / HiFi-GAN vs real-reference fixture           2.6e-6 .. 1.1e-5           4e-5    (same kernels)    2e-4
   5-step latent / mel (relative rms)                 2.0e-6..2.2e-6 / 3.1e-6    1e-5 / 1.5e-5   9.8e-6..1.05e-5 / 1.6e-5   1e-4
   200-step latent / mel (relative rms)               9.5e-7 / 2.0e-6            5e-6 / 1e-5     2.7e-6 / 1.0e-5            1e-4
+
+"f16x3" with ONE outlier channel, against fp64, whole tensor / the columns only small channels feed (tests/test_f16x3_outliers_gpu.py,
+profiles/r07_f16x3_outlier_errors.txt; the bars are the fp32-grade ones above, "bf16x6" on the same inputs in brackets):
+
+  quantity                                                        measured f16x3 whole / sub-block      (bf16x6)             bar
+  LayerNorm -> Linear, gamma / beta channel x 2^8, x 2^12         3.6e-7 .. 2.6e-6 / 2.4e-7 .. 1.2e-6   (<= 2.7e-6 / 1.5e-6)   5e-6
+  GroupNorm + SiLU -> conv3x3, same, n up to 32768                4.1e-7 .. 1.5e-6 / 4.4e-7 .. 1.0e-6   (<= 1.6e-6 / 1.6e-6)   5e-6
+  Linear / conv3x3 weight row or column x 2^10                    3.1e-7 .. 7.7e-7 / 4.4e-7 .. 6.8e-7   (<= 5.9e-7 / 5.1e-7)   5e-6
+  LayerNorm -> GEGLU -> FF-out, gate / value row x 2^4 .. 2^12    3.9e-7 .. 1.9e-6 / 4.4e-7 .. 9.1e-7   (<= 1.1e-6 / 7.6e-7)   5e-6
+    ... one gate row x 2^8 under the former (R c + b)^2 bound     1.1e-6 / 3.4e-5 (fails the sub-block assert alone)           5e-6
+  LayerNorm -> QKV -> attention -> to_out, W_v / W_k column, row  5.6e-7 .. 5.8e-6 / 5.5e-7 .. 1.4e-6   (<= 7.0e-6 / 2.2e-6)   5e-6 (+ 2^-24 max|score| log2 e with W_k)
 """
 import os
 
