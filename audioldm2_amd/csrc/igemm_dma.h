@@ -293,13 +293,9 @@ void igemm_dma_kernel(const IgemmK p) {
                 f.b[j][q] = __builtin_bit_cast(bf16x8, sa[BM * 4 * NP + (o * NP + q) * BN + (wn * NT + j) * 32 + l31]);
     };
 
-    f32x16 acc[MT][NT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    f32x16 acc[MT][NT], sum[MT][NT];   // the running block and the closed blocks (acc_close_block, igemm_epilogue.h)
+    acc_zero(acc);
+    acc_zero(sum);
     auto mma_frags = [&](const Frag& f) {
         // smallest partial products first; NP = 2 uses the first three of {mid*hi, hi*mid, hi*hi}
         constexpr int PA_[6] = {NP == 3 ? 0 : 1, NP == 3 ? 2 : 0, NP == 3 ? 1 : 0, 0, 1, 0};
@@ -383,11 +379,15 @@ void igemm_dma_kernel(const IgemmK p) {
         if constexpr (ST) advance();
         st = st1;
     };
-    for (; t + NST < nk; ++t) body(std::true_type{});
+    while (t + NST < nk) {   // blocks of ACC_BLOCK_TILES steady k-tiles; the tail and the last tile belong to the last block
+        for (const int te = min(nk - NST, t + ACC_BLOCK_TILES); t < te; ++t) body(std::true_type{});
+        if (t + NST < nk) acc_close_block(acc, sum);
+    }
     for (; t + 1 < nk; ++t) body(std::false_type{});
     read_frags(f1, st, 1);   // last tile
     mma_frags(f0);
     mma_frags(f1);
+    acc_total(acc, sum);
 
     __syncthreads();   // every wave is past its last fragment read; nothing is in flight
 #if ALDM_DMA_ABLATE & 16

@@ -195,13 +195,9 @@ void igemm_dma_lw_kernel(const IgemmK p) {
             for (int q = 0; q < NP; ++q)
                 f.b[j][q] = __builtin_bit_cast(bf16x8, sa[BM * 4 * NP + (o * NP + q) * BN + (wn * NT + j) * 32 + l31]);
     };
-    f32x16 acc[MT][NT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    f32x16 acc[MT][NT], sum[MT][NT];   // the running block and the closed blocks (acc_close_block, igemm_epilogue.h)
+    acc_zero(acc);
+    acc_zero(sum);
     auto mma_frags = [&](const Frag& f) {
         constexpr int PA_[6] = {NP == 3 ? 0 : 1, NP == 3 ? 2 : 0, NP == 3 ? 1 : 0, 0, 1, 0};
         constexpr int PB_[6] = {NP == 3 ? 2 : 0, NP == 3 ? 0 : 1, NP == 3 ? 1 : 0, 1, 0, 0};
@@ -218,31 +214,35 @@ void igemm_dma_lw_kernel(const IgemmK p) {
     Frag f0, f1;
     read_frags(f0, 0, 0);
     int st = 0;
-    for (int t = 0; t + 1 < nk; ++t) {
-        read_frags(f1, st, 1);
-        mma_frags(f0);
+    for (int t = 0, te = 0; t + 1 < nk;) {   // blocks of ACC_BLOCK_TILES k-tiles; the last tile belongs to the last block
+        if (t) acc_close_block(acc, sum);
+        for (te = min(nk - 1, t + ACC_BLOCK_TILES); t < te; ++t) {
+            read_frags(f1, st, 1);
+            mma_frags(f0);
 #pragma unroll
-        for (int q = 0; q < NMF; ++q) {   // one fragment read behind each of the first MFMAs
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            if (q < NRD) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        const int st1 = st + 1 == NST ? 0 : st + 1;
-        __builtin_amdgcn_s_waitcnt((7 << 4) | (3 << 14) | 15);   // lgkmcnt(0): this wave is done reading stage st
-        __builtin_amdgcn_s_barrier();
-        read_frags(f0, st1, 0);
-        mma_frags(f1);
+            for (int q = 0; q < NMF; ++q) {   // one fragment read behind each of the first MFMAs
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                if (q < NRD) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            const int st1 = st + 1 == NST ? 0 : st + 1;
+            __builtin_amdgcn_s_waitcnt((7 << 4) | (3 << 14) | 15);   // lgkmcnt(0): this wave is done reading stage st
+            __builtin_amdgcn_s_barrier();
+            read_frags(f0, st1, 0);
+            mma_frags(f1);
 #pragma unroll
-        for (int q = 0; q < NMF; ++q) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 1);
-            if (q < NRD) __builtin_amdgcn_sched_group_barrier(0x100, 1, 1);
+            for (int q = 0; q < NMF; ++q) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 1);
+                if (q < NRD) __builtin_amdgcn_sched_group_barrier(0x100, 1, 1);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            st = st1;
         }
-        __builtin_amdgcn_sched_barrier(0);
-        st = st1;
     }
     read_frags(f1, st, 1);   // last k-tile
     mma_frags(f0);
     mma_frags(f1);
+    acc_total(acc, sum);
     __builtin_amdgcn_s_waitcnt((7 << 4) | (3 << 14) | 15);   // lgkmcnt(0)
     __builtin_amdgcn_s_barrier();   // every MMA wave is past its last fragment read: the ring becomes epilogue staging
     unscale_acc<F16>(acc, d.acc_scale);

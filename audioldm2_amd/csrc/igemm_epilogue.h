@@ -32,6 +32,43 @@ struct IgemmK {
 
 enum { PRE_NONE = 0, PRE_AFFINE = 1, PRE_AFFINE_SILU = 2, PRE_LRELU = 3, PRE_GENERIC = 4 };
 
+// Blocked accumulation of the bf16-split K loops.  A split product feeds 6 (3) MFMAs per 16 k into the accumulator, each rounding
+// at the running sum's magnitude: over K = 9216 that is 3456 roundings, 2.0e-6 .. 3.4e-6 of max|out| where fp32 arithmetic itself
+// loses 5e-7 (tests/test_tuned_geometries_gpu.py).  So the K loop accumulates ACC_BLOCK_TILES k-tiles (K = 1024) into `acc`, then
+// adds the block into `sum` and starts the next block from zero: the long sum sees one rounding per 1024 k.  A contraction of up
+// to one block (+ the loop's tail) gives bit for bit what a single accumulator gives (0 + acc is exact).
+constexpr int ACC_BLOCK_TILES = 32;
+template <int MT, int NT>
+__device__ __forceinline__ void acc_zero(f32x16 (&a)[MT][NT]) {
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int j = 0; j < NT; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) a[i][j][e] = 0.f;
+}
+template <int MT, int NT>
+__device__ __forceinline__ void acc_close_block(f32x16 (&acc)[MT][NT], f32x16 (&sum)[MT][NT]) {
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int j = 0; j < NT; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                sum[i][j][e] += acc[i][j][e];
+                acc[i][j][e] = 0.f;
+            }
+}
+template <int MT, int NT>
+__device__ __forceinline__ void acc_total(f32x16 (&acc)[MT][NT], const f32x16 (&sum)[MT][NT]) {
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int j = 0; j < NT; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[i][j][e] += sum[i][j][e];
+}
+
 using bf16x8 = __bf16 __attribute__((ext_vector_type(8)));
 using u32x2 = unsigned __attribute__((ext_vector_type(2)));
 using u32x4 = unsigned __attribute__((ext_vector_type(4)));

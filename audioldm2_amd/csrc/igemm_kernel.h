@@ -569,14 +569,26 @@ void igemm_kernel(const IgemmK p) {
             };
             const int n_full = (kt1 - kt0) / KGRP;  // iterations in which every wave group has a tile
             int it = 0;
-            for (; it + 3 < n_full; it += 2) {
-                body(r0, r1, it, 0, std::true_type{});
-                body(r1, r0, it + 1, 1, std::true_type{});
+            // Blocked accumulation (acc_close_block, igemm_epilogue.h) where the second accumulator is free: the 128x128 tiles
+            // without an affine prologue keep it in registers they had to spare.  Every other instantiation spills with it
+            // (the 64-row / 64-column tiles 2 .. 150 VGPRs more) and keeps the single accumulator: the tables send no
+            // K >= 3072 launch at split-K 1 there.
+            constexpr bool BLOCKED = BM == 128 && BN == 128 && (PRE == PRE_NONE || PRE == PRE_LRELU);
+            f32x16 sum[BLOCKED ? MT : 1][BLOCKED ? NT : 1];
+            acc_zero(sum);
+            while (it + 3 < n_full) {
+                for (const int ie = BLOCKED ? min(n_full - 3, it + ACC_BLOCK_TILES) : n_full - 3; it < ie; it += 2) {
+                    body(r0, r1, it, 0, std::true_type{});
+                    body(r1, r0, it + 1, 1, std::true_type{});
+                }
+                if constexpr (BLOCKED)
+                    if (it + 3 < n_full) acc_close_block(acc, sum);
             }
             for (; it < n_it; it += 2) {  // `it` is even here: same stage roles as in the steady loop
                 body(r0, r1, it, 0, std::false_type{});
                 if (it + 1 < n_it) body(r1, r0, it + 1, 1, std::false_type{});
             }
+            if constexpr (BLOCKED) acc_total(acc, sum);
         }
     }
 

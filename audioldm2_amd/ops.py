@@ -625,10 +625,11 @@ def pack_geglu(weight: torch.Tensor, bias: Optional[torch.Tensor]) -> Packed:
     return pw
 
 
-def linear_geglu(x, pw: Packed, split_out: Optional[str] = None, gate_act: int = ACT_NONE):
+def linear_geglu(x, pw: Packed, split_out: Optional[str] = None, gate_act: int = ACT_NONE,
+                 out: Optional[torch.Tensor] = None):
     """y = value * gelu_erf(gate) with [value | gate] = x @ W^T + b fused into the GEMM epilogue
     (attention.py:37-45); pw from pack_geglu.  x: [..., Cin] fp32 or SplitT -> [..., N/2] (split_out: None -> fp32,
-    "only" -> SplitT, "also" -> (fp32, SplitT))."""
+    "only" -> SplitT, "also" -> (fp32, SplitT)); out: the caller's fp32 buffer for the result, as ops.conv takes one."""
     is_split = isinstance(x, SplitT)
     if not is_split:
         _chk(x, "linear_geglu.x")
@@ -636,7 +637,14 @@ def linear_geglu(x, pw: Packed, split_out: Optional[str] = None, gate_act: int =
     M = (x.rows if is_split else x.numel() // shp[-1])
     assert shp[-1] == pw.Cin and pw.KH == 1 and pw.KW == 1 and pw.N % 64 == 0
     oshape = (*shp[:-1], pw.N // 2)
-    out = None if split_out == "only" else torch.empty(oshape, device=x.device, dtype=torch.float32)
+    if split_out == "only":
+        assert out is None
+    elif out is None:
+        out = torch.empty(oshape, device=x.device, dtype=torch.float32)
+    else:
+        _chk(out, "linear_geglu.out")
+        assert out.numel() == M * (pw.N // 2), (out.shape, oshape)
+        out = out.view(oshape)
     so = None
     if split_out:
         if is_split and x.fmt == "f16" and x.rn > 0.0 and f16_mode() and F16_FF_OUT:

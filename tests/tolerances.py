@@ -14,6 +14,22 @@ operand significands, which keeps its own (looser) bars.
   5-step latent / mel (relative rms)                 2.0e-6..2.2e-6 / 3.1e-6    1e-5 / 1.5e-5   9.8e-6..1.05e-5 / 1.6e-5   1e-4
   200-step latent / mel (relative rms)               9.5e-7 / 2.0e-6            5e-6 / 1e-5     2.7e-6 / 1.0e-5            1e-4
 
+Every entry of the four shipped tuning tables at its real size, on the kernel it names, against an fp64 tap sum evaluated on the GPU
+(tests/test_tuned_geometries_gpu.py, profiles/r08_tuned_geometry_errors.txt; whole tensor / worst 32-column block on its own max|ref|),
+measured on the kernels whose K loop accumulates in blocks of K = 1024 (acc_close_block, csrc/igemm_epilogue.h); every case passes:
+
+  table (mode)                                    plain epilogue: whole / worst block (bar)         prologue / GEGLU / f16x3 (bar)
+  mi355x_igemm.json (f32)                         1.4e-7 .. 1.6e-6 / 2.0e-7 .. 1.8e-6 (2e-6)        1.2e-7 .. 4.0e-6 / 1.8e-7 .. 4.3e-6 (5e-6)
+  mi355x_igemm_bf16x6.json (bf16x6, fp32 A)       2.4e-7 .. 1.0e-6 / 3.1e-7 .. 1.2e-6 (2e-6)        1.2e-7 .. 1.4e-6 / 1.7e-7 .. 1.5e-6 (5e-6)
+  mi355x_igemm_dma.json (bf16x6, 3-part image)    2.4e-7 .. 9.6e-7 / 2.7e-7 .. 1.0e-6 (2e-6)        4.7e-7 .. 7.7e-7 / 6.8e-7 .. 1.3e-6 (5e-6)
+  mi355x_igemm_dma_bf16x3.json (bf16x3, 2-part)   2.0e-6 .. 3.8e-6 / 2.6e-6 .. 3.9e-6 (5e-5)        3.1e-6 .. 4.5e-6 / 6.5e-6 .. 6.6e-6 (5e-5)
+  mi355x_igemm_dma_bf16x3.json (f16x3, fp16)      —                                                 1.4e-7 .. 5.5e-7 / 1.7e-7 .. 7.6e-7 (5e-6)
+  plain entries with K >= 3072 at split-K 1 ("bf16x6"): DMA table (42) 3.9e-7 .. 7.3e-7 / 4.7e-7 .. 7.6e-7, bf16x6 table (3) 4.3e-7 .. 5.3e-7 /
+  5.0e-7 .. 6.7e-7; torch fp32 matmul over the same taps, every K >= 3072 entry: 2.2e-7 .. 8.0e-7 / 2.8e-7 .. 9.8e-7.
+  Before the blocked K loop (one fp32 accumulator over the whole contraction) 23 of those entries, K = 3072 .. 11520, measured 2.0e-6 ..
+  3.0e-6 / up to 3.4e-6 and failed the 2e-6 bar; the bar stayed and the kernels changed.  The one f32-table entry of that class (K = 3456,
+  128x64 tile, fp32 MFMA, single accumulator: the instantiations that keep it are listed in DESIGN.md 5) measures 1.6e-6 / 1.8e-6.
+
 "f16x3" with ONE outlier channel, against fp64, whole tensor / the columns only small channels feed (tests/test_f16x3_outliers_gpu.py,
 profiles/r07_f16x3_outlier_errors.txt; the bars are the fp32-grade ones above, "bf16x6" on the same inputs in brackets):
 
@@ -40,6 +56,20 @@ def fp32_grade(mode=None):
 def gemm_tol(mode=None):
     """One contraction against fp64 of the same fp32 inputs (max|err| / max|ref|)."""
     return 2e-6 if fp32_grade(mode) else 5e-5
+
+
+# Contractions of K >= LONG_K are also put next to torch's own fp32 matmul over the same taps (tests/test_tuned_geometries_gpu.py):
+# the yardstick of what fp32 arithmetic itself loses on the case.
+LONG_K = 3072
+
+
+def act_act_long_k_tol():
+    """Activation x activation products (ops.gemm_nt / ops.gemm_packed_batched: the VAE mid attention, 8 x [4096 x 4096] . [4096 x
+    512]) with K >= LONG_K and operands of non-zero mean, on the fp32 MFMA in every mode.  Measured on an MI355X against fp64: the
+    kernel 3.38e-6 whole / 3.61e-6 worst 32-column block, torch's fp32 bmm on the same operands 3.55e-6 / 3.79e-6
+    (profiles/r08_tuned_geometry_errors.txt) — fp32 accumulation itself sits above gemm_tol's 2e-6 there.  The bar is at most twice
+    the independent fp32 figure (7.1e-6): 5e-6."""
+    return 5e-6
 
 
 def fused_tol(mode=None):
