@@ -130,6 +130,72 @@ __global__ void ddim_step_indexed_kernel(float* __restrict__ x, const float* __r
     }
 }
 
+// ---- PLMS (pseudo linear multistep, plms.py:261-360): sigma = 0, so no noise operand ------------------------------------------
+// the step's model output: the optional CFG combine of eps[2, n], coef[5] / coef[6] as in ddim_step_kernel
+__device__ __forceinline__ float plms_model_out(const float* __restrict__ eps, int64_t i, int64_t n, bool cfg, float gs) {
+    if (cfg) {
+        const float eu = eps[i], ec = eps[n + i];
+        return eu + gs * (ec - eu);
+    }
+    return eps[i];
+}
+
+// Step 0 (plms.py:341-345, pseudo improved Euler).  e_next == nullptr: the provisional x_out = update(x, e_t), nothing else
+// is written but pred_x0.  Otherwise e' = (e_t + e_next) / 2, x_out = update(x, e'), and e_t opens the history ring (slot 0).
+// x_out may be x itself: every element is read before it is written, by the thread that writes it.
+__global__ void plms_first_step_kernel(const float* x, const float* __restrict__ e_t, const float* __restrict__ e_next,
+                                       const float* __restrict__ coef, float* x_out, float* __restrict__ pred_x0,
+                                       float* __restrict__ hist, int64_t n) {
+    const float c0 = coef[0], c1 = coef[1], c2 = coef[2], c3 = coef[3], gs = coef[5];
+    const bool cfg = coef[6] != 0.f;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const float e = plms_model_out(e_t, i, n, cfg, gs);
+        float ep = e;
+        if (e_next) {
+            ep = (e + plms_model_out(e_next, i, n, cfg, gs)) / 2.0f;
+            hist[i] = e;
+        }
+        const float p0 = (x[i] - c0 * ep) / c1;
+        x_out[i] = c3 * p0 + c2 * ep;
+        if (pred_x0) pred_x0[i] = p0;
+    }
+}
+
+// Steps >= 1 with the order, the coefficient row and the ring slots selected ON THE DEVICE by the step counter, in place on x:
+// one captured graph serves every step.  The model output of step j lives in ring slot j % 3, so at step s the newest entry
+// is slot (s - 1) % 3 and e_t goes where the oldest was, slot s % 3 — no rotation, no pointer swap.  Every thread reads its
+// element of all slabs before it writes its one slot.  Sums in the reference's order (plms.py:346-356), then the division.
+__global__ void plms_step_indexed_kernel(float* __restrict__ x, const float* __restrict__ eps, float* hist,
+                                         const float* __restrict__ coef_tab, const int* __restrict__ step_idx,
+                                         float* __restrict__ pred_x0, int64_t n, int coef_ld) {
+    const int s = *step_idx;
+    if (s < 1) return;   // step 0 has no history: plms_first_step_kernel
+    const int k = s < 3 ? s : 3;
+    const float* coef = coef_tab + (int64_t)s * coef_ld;
+    const float c0 = coef[0], c1 = coef[1], c2 = coef[2], c3 = coef[3], gs = coef[5];
+    const bool cfg = coef[6] != 0.f;
+    const float* h1 = hist + (int64_t)((s + 2) % 3) * n;
+    const float* h2 = hist + (int64_t)((s + 1) % 3) * n;
+    float* h3 = hist + (int64_t)(s % 3) * n;   // the oldest entry (read only at order 3), then e_t's slot
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const float e = plms_model_out(eps, i, n, cfg, gs);
+        float ep;
+        if (k == 1) {
+            ep = (3.0f * e - h1[i]) / 2.0f;
+        } else if (k == 2) {
+            ep = (23.0f * e - 16.0f * h1[i] + 5.0f * h2[i]) / 12.0f;
+        } else {
+            ep = (55.0f * e - 59.0f * h1[i] + 37.0f * h2[i] - 9.0f * h3[i]) / 24.0f;
+        }
+        const float p0 = (x[i] - c0 * ep) / c1;
+        x[i] = c3 * p0 + c2 * ep;
+        if (pred_x0) pred_x0[i] = p0;
+        h3[i] = e;
+    }
+}
+
 // last node of the step graph: counter += 1 and the NEXT step's timestep row into the UNet's static input (one block: every
 // thread reads the old counter before thread 0 stores the new one)
 __global__ void step_advance_kernel(int* __restrict__ step_idx, const float* __restrict__ t_tab, float* __restrict__ t_cur,
@@ -263,6 +329,24 @@ extern "C" int aldm_ddim_step_indexed(float* x, const float* eps, const float* n
     hipLaunchKernelGGL(ddim_step_indexed_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, x, eps, noise_tab,
                        coef_tab, step_idx, pred_x0, n, coef_ld);
     ALDM_LAUNCH_CHECK("aldm_ddim_step_indexed");
+    return 0;
+}
+
+extern "C" int aldm_plms_first_step(const float* x, const float* e_t, const float* e_next, const float* coef_row, float* x_out,
+                                    float* pred_x0, float* hist, int64_t n, void* stream) {
+    ALDM_CHECK(x && e_t && coef_row && x_out && n > 0 && (!e_next || hist), "aldm_plms_first_step: bad args");
+    hipLaunchKernelGGL(plms_first_step_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, x, e_t, e_next, coef_row,
+                       x_out, pred_x0, hist, n);
+    ALDM_LAUNCH_CHECK("aldm_plms_first_step");
+    return 0;
+}
+
+extern "C" int aldm_plms_step_indexed(float* x, const float* eps, float* hist, const float* coef_tab, const int* step_idx,
+                                      float* pred_x0, int64_t n, int coef_ld, void* stream) {
+    ALDM_CHECK(x && eps && hist && coef_tab && step_idx && n > 0 && coef_ld >= 7, "aldm_plms_step_indexed: bad args");
+    hipLaunchKernelGGL(plms_step_indexed_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, x, eps, hist, coef_tab,
+                       step_idx, pred_x0, n, coef_ld);
+    ALDM_LAUNCH_CHECK("aldm_plms_step_indexed");
     return 0;
 }
 

@@ -1419,6 +1419,48 @@ def ddim_step_indexed(x: torch.Tensor, eps: torch.Tensor, noise_tab: torch.Tenso
     return x
 
 
+def plms_first_step(x: torch.Tensor, e_t: torch.Tensor, e_next: Optional[torch.Tensor], coef: torch.Tensor,
+                    x_out: Optional[torch.Tensor] = None, pred_x0: Optional[torch.Tensor] = None,
+                    hist: Optional[torch.Tensor] = None):
+    """Step 0 of PLMS (aldm_plms_first_step).  e_next None: the provisional x_prev from e_t, out of place.  With e_next: the
+    update from (e_t + e_next) / 2 and e_t into slot 0 of the ring hist [3, *x.shape] (x_out may be x).  e_t / e_next:
+    [2, *x.shape] (uncond, cond) when coef[6] != 0, else [*x.shape]; coef: device row of >= 7 floats as in ddim_step."""
+    for t, n in ((x, "x"), (e_t, "e_t"), (coef, "coef")):
+        _chk(t, "plms_first." + n)
+    assert coef.numel() >= 7 and e_t.numel() in (x.numel(), 2 * x.numel())
+    if e_next is not None:
+        _chk(e_next, "plms_first.e_next"); _chk(hist, "plms_first.hist")
+        assert e_next.shape == e_t.shape and tuple(hist.shape) == (3,) + tuple(x.shape)
+    if x_out is None:
+        x_out = torch.empty_like(x)
+    if pred_x0 is None:
+        pred_x0 = torch.empty_like(x)
+    _chk(x_out, "plms_first.x_out"); _chk(pred_x0, "plms_first.pred_x0")
+    assert x_out.shape == x.shape == pred_x0.shape
+    _l.check(_l.load().aldm_plms_first_step(x.data_ptr(), e_t.data_ptr(), _p(e_next), coef.data_ptr(), x_out.data_ptr(),
+                                            pred_x0.data_ptr(), _p(hist if e_next is not None else None), x.numel(),
+                                            _stream()), "plms_first_step")
+    return x_out, pred_x0
+
+
+def plms_step_indexed(x: torch.Tensor, eps: torch.Tensor, hist: torch.Tensor, coef_tab: torch.Tensor,
+                      step_idx: torch.Tensor, pred_x0: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """A PLMS step >= 1 in place on x (aldm_plms_step_indexed): multistep order min(step_idx, 3), coefficient row and ring
+    slots selected on the device by the int32 counter `step_idx`; the step's model output replaces the oldest entry of the
+    ring hist [3, *x.shape].  eps: [2, *x.shape] when the row's coef[6] != 0, else [*x.shape]; coef_tab: [S, >= 7]."""
+    for t, n in ((x, "x"), (eps, "eps"), (hist, "hist"), (coef_tab, "coef_tab")):
+        _chk(t, "plms_indexed." + n)
+    assert step_idx.dtype == torch.int32 and step_idx.is_cuda and coef_tab.dim() == 2
+    assert tuple(hist.shape) == (3,) + tuple(x.shape) and eps.numel() in (x.numel(), 2 * x.numel())
+    if pred_x0 is not None:
+        _chk(pred_x0, "plms_indexed.pred_x0")
+        assert pred_x0.shape == x.shape
+    _l.check(_l.load().aldm_plms_step_indexed(x.data_ptr(), eps.data_ptr(), hist.data_ptr(), coef_tab.data_ptr(),
+                                              step_idx.data_ptr(), _p(pred_x0), x.numel(), coef_tab.shape[1], _stream()),
+             "plms_step_indexed")
+    return x
+
+
 def step_advance(step_idx: torch.Tensor, t_tab: torch.Tensor, t_cur: torch.Tensor) -> None:
     """step_idx += 1; t_cur = t_tab[min(step_idx, S - 1)] on the device (aldm_step_advance)."""
     _chk(t_tab, "step_advance.t_tab"); _chk(t_cur, "step_advance.t_cur")

@@ -515,7 +515,12 @@ class LatentDiffusion(nn.Module):
         else:
             shape = (self.channels, self.latent_t_size, self.latent_f_size)
         if use_plms:
-            raise NotImplementedError("PLMS is never selected by the public API (use_plms=False); out of scope")
+            # ddpm.py:1449-1461 (mask / x0 / eta travel on; eta != 0 raises in PLMSSampler.make_schedule)
+            from .plms import PLMSSampler
+            samples, _ = PLMSSampler(self).sample(ddim_steps, batch_size, shape, cond, verbose=False,
+                                                  unconditional_guidance_scale=unconditional_guidance_scale, mask=mask,
+                                                  unconditional_conditioning=unconditional_conditioning, **kwargs)
+            return samples, None
         if not ddim:
             kwargs.pop("eta", None)  # the ancestral sampler has no eta (the reference would raise here)
             samples = self.sample(cond=cond, batch_size=batch_size, mask=mask, **kwargs)
@@ -722,6 +727,8 @@ class LatentDiffusion(nn.Module):
         draws the posterior sample (one CPU randn of the latent shape, distributions.py:37-41) only to
         read its batch size; we replay the draw and skip the 345 GFLOP encode."""
         assert x_T is None
+        if use_plms:
+            assert ddim_steps is not None
         self.check_latent_t(self.latent_t_size)
         self._check_candidates(n_gen, batch.get("text"))
         use_ddim = ddim_steps is not None
@@ -806,6 +813,8 @@ class LatentDiffusion(nn.Module):
         """ddpm.py:1573-1676 (inpainting / super-resolution): VAE-encode the given mel -> x0, keep the
         unmasked latent region (DDIM blends q_sample(x0, t) back in every step), regenerate the rest."""
         assert x_T is None
+        if use_plms:
+            assert ddim_steps is not None
         self._check_candidates(n_gen, batch.get("text"))
         use_ddim = ddim_steps is not None
         fb = batch["log_mel_spec"] if self.first_stage_key == "fbank" else batch[self.first_stage_key]

@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 /* ---- library / error ------------------------------------------------------------------ */
-int aldm_version(void);              /* ABI version (10), bumped on any struct / entry change */
+int aldm_version(void);              /* ABI version (11), bumped on any struct / entry change */
 const char* aldm_last_error(void);   /* message of the last failing call on this thread     */
 
 /* ---- activations usable as prologue (applied to the gathered input) or epilogue -------- */
@@ -468,6 +468,19 @@ int aldm_ddim_step(const float* x, const float* eps, const float* noise, const f
  * aldm_step_advance it lets one captured HIP graph serve every DDIM step with no host-issued copy between replays.   */
 int aldm_ddim_step_indexed(float* x, const float* eps, const float* noise_tab, const float* coef_tab,
                            const int* step_idx, float* pred_x0, int64_t n, int coef_ld, void* stream);
+/* PLMS (plms.py:261-360; ABI v11).  sigma = 0 (make_schedule refuses any other eta): no noise operand.  eps / e_t / e_next hold
+ * [e_uncond ; e_cond] ([2, n]) when coef[6] != 0, else [1, n]; coef rows as in aldm_ddim_step (coef[4] unused).  The history ring
+ * hist[3, n] keeps the model output of step j — after the guidance combine, before the multistep combine — in slot j % 3.
+ * aldm_plms_first_step, step 0 (pseudo improved Euler): e_next == NULL writes the provisional x_out = update(x, e_t) and pred_x0
+ * (hist untouched, may be NULL); with e_next, e' = (e_t + e_next) / 2, x_out = update(x, e'), hist[0] = e_t.  x_out may be x.
+ * aldm_plms_step_indexed, steps >= 1, in place on x: s = *step_idx, coef = coef_tab[s], order k = min(s, 3),
+ *   e' = (3 e - h1) / 2 | (23 e - 16 h1 + 5 h2) / 12 | (55 e - 59 h1 + 37 h2 - 9 h3) / 24   with h_j = hist[(s - j) % 3],
+ *   pred_x0 = (x - c0*e')/c1; x = c3*pred_x0 + c2*e'; hist[s % 3] = e.   A launch that finds s == 0 writes nothing.
+ * With aldm_step_advance one captured HIP graph serves every step >= 1 (ring slots follow the counter: no host rotation).   */
+int aldm_plms_first_step(const float* x, const float* e_t, const float* e_next, const float* coef_row, float* x_out,
+                         float* pred_x0, float* hist, int64_t n, void* stream);
+int aldm_plms_step_indexed(float* x, const float* eps, float* hist, const float* coef_tab, const int* step_idx,
+                           float* pred_x0, int64_t n, int coef_ld, void* stream);
 /* *step_idx += 1 and t_cur[0..nt) = t_tab[min(*step_idx, steps-1)] (the next step's timestep row, the UNet's static input;
  * the time_range of ddim.py:205-213 stored as floats, one row per step in loop order)                                  */
 int aldm_step_advance(int* step_idx, const float* t_tab, float* t_cur, int nt, int steps, void* stream);
