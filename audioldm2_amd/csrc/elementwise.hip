@@ -196,6 +196,69 @@ __global__ void plms_step_indexed_kernel(float* __restrict__ x, const float* __r
     }
 }
 
+// ---- DPM-Solver++(2M) (Lu et al. 2022, Algorithm 2), deterministic, data-prediction form ----------------------------------------
+// Row s = *step_idx of coef_tab = {sigma_t, alpha_t, sigma_prev / sigma_t, -alpha_prev * expm1(-h), w, guidance scale, cfg flag}:
+//   x0 = (x - sigma_t e) / alpha_t;  D = x0 (w == 0: a first-order step) or x0 + w (x0 - x0_last);  x = c2 x + c3 D;  x0_last = x0.
+struct dpmpp_row {
+    float c0, c1, c2, c3, w, gs;
+    bool cfg, second;
+};
+
+__device__ __forceinline__ dpmpp_row dpmpp_load_row(const float* __restrict__ coef_tab, const int* __restrict__ step_idx, int coef_ld) {
+    const float* coef = coef_tab + (int64_t)*step_idx * coef_ld;
+    return {coef[0], coef[1], coef[2], coef[3], coef[4], coef[5], coef[6] != 0.f, coef[4] != 0.f};
+}
+
+// one element: x and x0 are updated in place; `old` (the previous step's x0) is read only on a second-order step
+__device__ __forceinline__ void dpmpp_elem(const dpmpp_row& r, float& x, float eu, float ec, float old, float& x0) {
+    const float e = r.cfg ? eu + r.gs * (ec - eu) : eu;
+    const float p0 = (x - r.c0 * e) / r.c1;
+    const float d = r.second ? p0 + r.w * (p0 - old) : p0;
+    x = r.c2 * x + r.c3 * d;
+    x0 = p0;
+}
+
+// x0_buf is the one-slab history AND the pred_x0 output: each thread reads its old element, then writes the new x0.  With w == 0
+// the old element is not even loaded, so an uninitialised (or NaN) slab cannot reach x.  The counter is trusted as in
+// ddim_step_indexed_kernel: step_advance_kernel saturates it at the table's last row.
+__global__ void dpmpp_step_indexed_kernel(float* __restrict__ x, const float* __restrict__ eps, float* __restrict__ x0_buf,
+                                          const float* __restrict__ coef_tab, const int* __restrict__ step_idx, int64_t n,
+                                          int coef_ld) {
+    const dpmpp_row r = dpmpp_load_row(coef_tab, step_idx, coef_ld);
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        float xv = x[i], p0;
+        dpmpp_elem(r, xv, eps[i], r.cfg ? eps[n + i] : 0.f, r.second ? x0_buf[i] : 0.f, p0);
+        x[i] = xv;
+        x0_buf[i] = p0;
+    }
+}
+
+// the same with 16 bytes per lane and access: n4 = n / 4 for n % 4 == 0 and 16-byte aligned operands (so is eps + n then)
+__global__ void dpmpp_step_indexed_vec4_kernel(float* __restrict__ x, const float* __restrict__ eps, float* __restrict__ x0_buf,
+                                               const float* __restrict__ coef_tab, const int* __restrict__ step_idx, int64_t n4,
+                                               int coef_ld) {
+    const dpmpp_row r = dpmpp_load_row(coef_tab, step_idx, coef_ld);
+    f32x4* xq = reinterpret_cast<f32x4*>(x);
+    f32x4* hq = reinterpret_cast<f32x4*>(x0_buf);
+    const f32x4* eq = reinterpret_cast<const f32x4*>(eps);
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+        f32x4 xv = xq[i], p0;
+        const f32x4 eu = eq[i];
+        const f32x4 ec = r.cfg ? eq[n4 + i] : zero;
+        const f32x4 old = r.second ? hq[i] : zero;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float xk = xv[k], pk;
+            dpmpp_elem(r, xk, eu[k], ec[k], old[k], pk);
+            xv[k] = xk;
+            p0[k] = pk;
+        }
+        xq[i] = xv;
+        hq[i] = p0;
+    }
+}
+
 // last node of the step graph: counter += 1 and the NEXT step's timestep row into the UNet's static input (one block: every
 // thread reads the old counter before thread 0 stores the new one)
 __global__ void step_advance_kernel(int* __restrict__ step_idx, const float* __restrict__ t_tab, float* __restrict__ t_cur,
@@ -347,6 +410,22 @@ extern "C" int aldm_plms_step_indexed(float* x, const float* eps, float* hist, c
     hipLaunchKernelGGL(plms_step_indexed_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, x, eps, hist, coef_tab,
                        step_idx, pred_x0, n, coef_ld);
     ALDM_LAUNCH_CHECK("aldm_plms_step_indexed");
+    return 0;
+}
+
+extern "C" int aldm_dpmpp_step_indexed(float* x, const float* eps, float* x0_buf, const float* coef_tab, const int* step_idx,
+                                       int64_t n, int coef_ld, void* stream) {
+    ALDM_CHECK(x && eps && x0_buf && coef_tab && step_idx, "aldm_dpmpp_step_indexed: null pointer");
+    ALDM_CHECK(n > 0 && coef_ld >= 7, "aldm_dpmpp_step_indexed: bad args (n=%lld, coef_ld=%d: rows of >= 7 floats)", (long long)n,
+               coef_ld);
+    const bool vec = n % 4 == 0 && (((uintptr_t)x | (uintptr_t)eps | (uintptr_t)x0_buf) & 15) == 0;
+    if (vec)
+        hipLaunchKernelGGL(dpmpp_step_indexed_vec4_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, x, eps, x0_buf,
+                           coef_tab, step_idx, n / 4, coef_ld);
+    else
+        hipLaunchKernelGGL(dpmpp_step_indexed_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, x, eps, x0_buf,
+                           coef_tab, step_idx, n, coef_ld);
+    ALDM_LAUNCH_CHECK("aldm_dpmpp_step_indexed");
     return 0;
 }
 

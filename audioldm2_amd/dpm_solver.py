@@ -1,0 +1,207 @@
+"""DPM-Solver++(2M) sampler on MI355X (Lu et al. 2022, "DPM-Solver++", Algorithm 2): the deterministic second-order multistep
+solver in its data-prediction form, over the model's eps output.  It has no counterpart in the reference; the class carries
+PLMSSampler's parameter lists and `(samples, intermediates)` return, and is selected by name: `sampler="dpmpp_2m"` in
+`LatentDiffusion.sample_log` / `generate_batch` / `generate_batch_masked` / `text_to_audio` / `super_resolution_and_inpainting`.
+
+One step from abar_t to abar_prev — DDIM's `ddim_alphas[index]` and `ddim_alphas_prev[index]`, so the last step lands on
+`alphas_cumprod[0]` — with alpha = sqrt(abar), sigma = sqrt(1 - abar), lambda = log(alpha / sigma), h = lambda_prev - lambda_t > 0:
+    e  = e_u + s (e_c - e_u)                                  guidance combine
+    x0 = (x - sigma_t e) / alpha_t
+    D  = x0                                                   first-order step
+       = x0 + w (x0 - x0_last),  w = 1 / (2 r), r = h_last / h   otherwise
+    x  = (sigma_prev / sigma_t) x - alpha_prev expm1(-h) D ;  x0_last = x0
+Step 0 is first order (no history yet); the last step is first order when the run has fewer than 15 steps ("lower order final":
+the last interval has by far the largest h on the uniform grid and the linear extrapolation overshoots there on short runs).  A
+first-order step is algebraically the DDIM eta = 0 step.
+
+On MI355X:
+  * guidance combine + x0 + extrapolation + update + history are one kernel per step (ops.dpmpp_step_indexed); the history is ONE
+    slab, which is also the pred_x0 output;
+  * the order of a step is a column of its coefficient row (w = 0: first order, the slab is not read), so EVERY step, step 0
+    included, is the same launch sequence on one stream: UNet pass -> dpmpp_step_indexed -> step_advance, run eagerly once,
+    captured into a HIP graph at the second step and replayed after (ddim.GraphStepper).  The graph lives for one sampling run;
+    nothing is read from or written to the UNet's DDIM graph cache;
+  * the coefficient table is built in fp64 from the fp32 `alphas_cumprod` buffer and rounded once to fp32
+    (dpmpp_2m_coefficients);
+  * RNG: the solver is deterministic and there is no reference implementation whose discarded draws would have to be mirrored.
+    The host generator is consumed by x_T (when not given) and, when inpainting, by one `q_sample` draw per step — and by
+    nothing else.
+"""
+from __future__ import annotations
+
+import os
+
+import numpy as np
+import torch
+
+from . import ops
+from .ddim import GraphStepper, host_drawer, make_ddim_sampling_parameters, make_ddim_timesteps
+
+LOWER_ORDER_FINAL_BELOW = 15   # runs shorter than this take their last step at first order
+
+
+def dpmpp_2m_coefficients(alphas, alphas_prev):
+    """Pure host function: the [S, 5] fp64 rows {sigma_t, alpha_t, sigma_prev / sigma_t, -alpha_prev expm1(-h), w} of a run whose
+    step i goes from abar = alphas[i] to alphas_prev[i] (step order: the noisiest step first).  w = 1 / (2 r) with r = h_last / h
+    and h_last the previous step's h; w = 0 marks a first-order step: row 0, and the last row when S < 15."""
+    a_t = np.asarray(alphas, dtype=np.float64).reshape(-1)
+    a_p = np.asarray(alphas_prev, dtype=np.float64).reshape(-1)
+    assert a_t.shape == a_p.shape
+    S = a_t.shape[0]
+    alpha_t, sigma_t = np.sqrt(a_t), np.sqrt(1.0 - a_t)
+    alpha_p, sigma_p = np.sqrt(a_p), np.sqrt(1.0 - a_p)
+    h = np.log(alpha_p / sigma_p) - np.log(alpha_t / sigma_t)
+    if not (np.all(np.isfinite(h)) and np.all(h > 0)):
+        raise ValueError("dpmpp_2m_coefficients: every step must go to a less noisy state (0 < abar_t < abar_prev < 1)")
+    w = np.zeros(S)
+    w[1:] = h[1:] / (2.0 * h[:-1])
+    if S < LOWER_ORDER_FINAL_BELOW:
+        w[S - 1:] = 0.0
+    return np.stack([sigma_t, alpha_t, sigma_p / sigma_t, -alpha_p * np.expm1(-h), w], 1)
+
+
+class DPMSolverSampler(object):
+    def __init__(self, model, schedule="linear", **kwargs):
+        super().__init__()
+        self.model = model
+        self.ddpm_num_timesteps = model.num_timesteps
+        self.schedule = schedule
+        self.use_graph = os.environ.get("ALDM_NO_GRAPH", "0") != "1"
+        # (global_batch, row_offset) when this process samples one shard of a larger batch (dist.py)
+        self.noise_shard = getattr(model, "noise_shard", None)
+
+    def register_buffer(self, name, attr):
+        setattr(self, name, attr)
+
+    def make_schedule(self, ddim_num_steps, ddim_discretize="uniform", ddim_eta=0.0, verbose=True):
+        """DDIM's timestep grid and abar tables at eta = 0 (host side), and the solver's coefficient table for the whole grid."""
+        if ddim_eta != 0:
+            raise ValueError("ddim_eta must equal 0 for DPM-Solver++(2M): the solver is deterministic")
+        self.ddim_timesteps = make_ddim_timesteps(ddim_discretize, ddim_num_steps, self.ddpm_num_timesteps, verbose)
+        alphas_cumprod = self.model.alphas_cumprod.detach().float().cpu()
+        assert alphas_cumprod.shape[0] == self.ddpm_num_timesteps, "alphas have to be defined for each timestep"
+        self.register_buffer("alphas_cumprod", alphas_cumprod)
+        self.register_buffer("sqrt_alphas_cumprod", torch.sqrt(alphas_cumprod))
+        self.register_buffer("sqrt_one_minus_alphas_cumprod", torch.sqrt(1.0 - alphas_cumprod))
+        sig, a, a_prev = make_ddim_sampling_parameters(alphas_cumprod, self.ddim_timesteps, ddim_eta, verbose)
+        self.register_buffer("ddim_sigmas", sig)
+        self.register_buffer("ddim_alphas", a)
+        self.register_buffer("ddim_alphas_prev", a_prev)
+        self.dpm_coef = self._table(len(self.ddim_timesteps))
+
+    def _table(self, total_steps):
+        """[total_steps, 5] fp32 rows in loop order for a run over the first `total_steps` grid entries (i = 0 is the noisiest
+        step, index = total_steps - 1): fp64 from the fp32 abar values, rounded once."""
+        a = np.asarray(self.ddim_alphas, dtype=np.float64)[:total_steps][::-1]
+        a_prev = np.asarray(self.ddim_alphas_prev, dtype=np.float64)[:total_steps][::-1]
+        return torch.from_numpy(dpmpp_2m_coefficients(a, a_prev)).float()
+
+    @torch.no_grad()
+    def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None,
+               img_callback=None, quantize_x0=False, eta=0.0, mask=None, x0=None, temperature=1.0,
+               noise_dropout=0.0, score_corrector=None, corrector_kwargs=None, verbose=True, x_T=None,
+               log_every_t=100, unconditional_guidance_scale=1.0, unconditional_conditioning=None, **kwargs):
+        """PLMSSampler.sample's parameter list; S is the grid parameter of make_ddim_timesteps."""
+        self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
+        C, H, W = shape
+        size = (batch_size, C, H, W)
+        return self.dpm_sampling(conditioning, size, callback=callback, img_callback=img_callback,
+                                 quantize_denoised=quantize_x0, mask=mask, x0=x0, ddim_use_original_steps=False,
+                                 noise_dropout=noise_dropout, temperature=temperature, score_corrector=score_corrector,
+                                 corrector_kwargs=corrector_kwargs, x_T=x_T, log_every_t=log_every_t,
+                                 unconditional_guidance_scale=unconditional_guidance_scale,
+                                 unconditional_conditioning=unconditional_conditioning)
+
+    # ------------------------------------------------------------------------------------------
+    @staticmethod
+    def _refuse(ddim_use_original_steps, quantize_denoised, score_corrector, noise_dropout):
+        if ddim_use_original_steps:
+            raise NotImplementedError("DPMSolverSampler(HIP): ddim_use_original_steps=True is not supported (the other samplers "
+                                      "refuse it too)")
+        if quantize_denoised or score_corrector is not None or noise_dropout != 0.0:
+            raise NotImplementedError("DPMSolverSampler(HIP): option not used by the AudioLDM2 pipeline")
+
+    def _model_output(self, x, t_row, b, cond, uncond, use_cfg, prepared):
+        """The UNet pass of one step: eps [2, b, ...] = [uncond ; cond] under guidance (combined inside the step kernel), else
+        eps [b, ...].  t_row: the step's timestep as floats, one entry per UNet row."""
+        if not use_cfg:
+            return self.model.apply_model(x, t_row[:b].long(), cond).contiguous()
+        if hasattr(self.model, "apply_model_cfg"):
+            return self.model.apply_model_cfg(x, t_row, cond, uncond, prepared=prepared)
+        tl = t_row[:b].long()
+        return torch.stack([self.model.apply_model(x, tl, uncond), self.model.apply_model(x, tl, cond)]).contiguous()
+
+    @torch.no_grad()
+    def dpm_sampling(self, cond, shape, x_T=None, ddim_use_original_steps=False, callback=None, timesteps=None,
+                     quantize_denoised=False, mask=None, x0=None, img_callback=None, log_every_t=100, temperature=1.0,
+                     noise_dropout=0.0, score_corrector=None, corrector_kwargs=None, unconditional_guidance_scale=1.0,
+                     unconditional_conditioning=None):
+        """PLMSSampler.plms_sampling's parameter list and loop structure."""
+        self._refuse(ddim_use_original_steps, quantize_denoised, score_corrector, noise_dropout)
+        dev = torch.device("cuda")
+        shape = tuple(shape)
+        b = shape[0]
+        ts = self.ddim_timesteps
+        if timesteps is not None:
+            # as DDIM and PLMS: sample only the first `subset_end` entries of the sequence (start from a less noisy state)
+            subset_end = int(min(timesteps / ts.shape[0], 1) * ts.shape[0]) - 1
+            ts = ts[:subset_end]
+        total_steps = ts.shape[0]
+        time_range = np.flip(ts).copy()   # own storage, positive strides: from_numpy refuses the flipped view, even of one entry
+        use_cfg = not (unconditional_conditioning is None or unconditional_guidance_scale == 1.0)
+        # the host generator: x_T first, then (inpainting only) one q_sample draw per step — nothing else
+        draw = host_drawer(shape, self.noise_shard)
+        img = (draw() if x_T is None else x_T.detach().float().cpu()).to(dev).contiguous()
+        intermediates = {"x_inter": [img], "pred_x0": [img]}
+        if total_steps == 0:
+            # `timesteps` <= one interval: the loop runs zero iterations and returns x_T
+            return img, intermediates
+
+        # device tables in loop order; a sub-range has its own table (its own first and last step)
+        coef = torch.zeros(total_steps, 8)
+        coef[:, :5] = self.dpm_coef if total_steps == self.dpm_coef.shape[0] else self._table(total_steps)
+        coef[:, 5] = float(unconditional_guidance_scale)
+        coef[:, 6] = 1.0 if use_cfg else 0.0
+        coef = coef.to(dev)
+        nrep = 2 if use_cfg else 1
+        t_tab = torch.from_numpy(time_range).float()[:, None].repeat(1, nrep * b).to(dev).contiguous()
+        if mask is not None:
+            assert x0 is not None
+            mask_d = mask.float().to(dev).expand(shape).contiguous()
+            x0_d = x0.float().to(dev).contiguous()
+            tr = torch.from_numpy(time_range)
+            blend_coef = torch.stack([self.sqrt_alphas_cumprod[tr], self.sqrt_one_minus_alphas_cumprod[tr]],
+                                     1).contiguous().to(dev)  # [S, 2] = {sqrt(abar_t), sqrt(1 - abar_t)}
+        prepared = self.model.prepare_cfg(cond, unconditional_conditioning) \
+            if use_cfg and hasattr(self.model, "apply_model_cfg") and hasattr(self.model, "prepare_cfg") else None
+
+        # static buffers = the inputs of the step graph.  pred_x0 is the solver's history slab: step 0 (w = 0) does not read it
+        x_cur, pred_x0 = img.clone(), torch.empty_like(img)
+        step_idx = torch.zeros(1, device=dev, dtype=torch.int32)
+        t_cur = t_tab[0].clone()
+
+        def step():
+            eps = self._model_output(x_cur, t_cur, b, cond, unconditional_conditioning, use_cfg, prepared)
+            ops.dpmpp_step_indexed(x_cur, eps, pred_x0, coef, step_idx)
+            ops.step_advance(step_idx, t_tab, t_cur)
+        run_step = GraphStepper(step, self.use_graph)   # every step: eager once, captured at the next, replayed after
+        for i, _ in enumerate(time_range):
+            index = total_steps - i - 1
+            if mask is not None:
+                # img = q_sample(x0, ts)*mask + (1-mask)*img, between the replays; its draw comes first
+                ops.inpaint_blend(x_cur, x0_d, draw().to(dev), mask_d, blend_coef[i])
+            run_step()
+            if callback:
+                callback(i)
+            if img_callback:
+                img_callback(pred_x0, i)
+            if index % log_every_t == 0 or index == total_steps - 1:
+                intermediates["x_inter"].append(x_cur.clone())
+                intermediates["pred_x0"].append(pred_x0.clone())
+        out = x_cur.clone()
+        # the stepper, its graph and the step closure form a reference cycle: break it here, where no stream is capturing and
+        # no replay is in flight, instead of leaving the graph and its memory pool to the cyclic collector (ddim.GraphStepper)
+        torch.cuda.synchronize()
+        run_step.fn = None
+        run_step.graph = None
+        return out, intermediates

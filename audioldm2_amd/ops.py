@@ -1461,6 +1461,21 @@ def plms_step_indexed(x: torch.Tensor, eps: torch.Tensor, hist: torch.Tensor, co
     return x
 
 
+def dpmpp_step_indexed(x: torch.Tensor, eps: torch.Tensor, x0_buf: torch.Tensor, coef: torch.Tensor,
+                       step_idx: torch.Tensor) -> torch.Tensor:
+    """A DPM-Solver++(2M) step in place on x (aldm_dpmpp_step_indexed): the coefficient row is selected on the device by the int32
+    counter `step_idx`; x0_buf [*x.shape] holds the previous step's x0 on entry (not read when the row's w == 0) and this step's
+    x0 — the pred_x0 output — on return.  eps: [2, *x.shape] when the row's coef[6] != 0, else [*x.shape]; coef: [S, >= 7] rows
+    {sigma_t, alpha_t, sigma_prev/sigma_t, -alpha_prev*expm1(-h), w, guidance scale, cfg flag}."""
+    for t, n in ((x, "x"), (eps, "eps"), (x0_buf, "x0_buf"), (coef, "coef")):
+        _chk(t, "dpmpp_indexed." + n)
+    assert step_idx.dtype == torch.int32 and step_idx.is_cuda and coef.dim() == 2
+    assert x0_buf.shape == x.shape and eps.numel() in (x.numel(), 2 * x.numel())
+    _l.check(_l.load().aldm_dpmpp_step_indexed(x.data_ptr(), eps.data_ptr(), x0_buf.data_ptr(), coef.data_ptr(),
+                                               step_idx.data_ptr(), x.numel(), coef.shape[1], _stream()), "dpmpp_step_indexed")
+    return x
+
+
 def step_advance(step_idx: torch.Tensor, t_tab: torch.Tensor, t_cur: torch.Tensor) -> None:
     """step_idx += 1; t_cur = t_tab[min(step_idx, S - 1)] on the device (aldm_step_advance)."""
     _chk(t_tab, "step_advance.t_tab"); _chk(t_cur, "step_advance.t_cur")

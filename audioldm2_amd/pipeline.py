@@ -274,6 +274,21 @@ class DiffusionWrapper(nn.Module):
                                     context_attn_mask_list=masks)
 
 
+SAMPLERS = ("dpmpp_2m",)   # what `sampler=` names besides the reference's own choices (DDIM, use_plms=True, ancestral)
+
+
+def resolve_sampler(sampler, use_plms=False):
+    """The `sampler=` keyword of sample_log / generate_batch / generate_batch_masked / text_to_audio /
+    super_resolution_and_inpainting: None (the reference's behaviour) or a name in SAMPLERS, not together with use_plms=True."""
+    if sampler is None:
+        return None
+    if sampler not in SAMPLERS:
+        raise ValueError(f"unknown sampler {sampler!r}: expected None or one of {SAMPLERS}")
+    if use_plms:
+        raise ValueError(f"sampler={sampler!r} and use_plms=True name two samplers: pass one")
+    return sampler
+
+
 class LatentDiffusion(nn.Module):
     """Sampling-path subset of ddpm.py's DDPM/LatentDiffusion with identical public signatures.
     State-dict layout is the reference's: `model.diffusion_model.*`, `first_stage_model.*`,
@@ -509,7 +524,8 @@ class LatentDiffusion(nn.Module):
     @torch.no_grad()
     def sample_log(self, cond, batch_size, ddim, ddim_steps, unconditional_guidance_scale=1.0,
                    unconditional_conditioning=None, use_plms=False, mask=None, **kwargs):
-        """ddpm.py:1418-1474"""
+        """ddpm.py:1418-1474; `sampler="dpmpp_2m"` (a keyword of **kwargs, no reference counterpart) runs DPMSolverSampler."""
+        sampler_name = resolve_sampler(kwargs.pop("sampler", None), use_plms)
         if mask is not None:
             shape = (self.channels, mask.size()[-2], mask.size()[-1])
         else:
@@ -520,6 +536,15 @@ class LatentDiffusion(nn.Module):
             samples, _ = PLMSSampler(self).sample(ddim_steps, batch_size, shape, cond, verbose=False,
                                                   unconditional_guidance_scale=unconditional_guidance_scale, mask=mask,
                                                   unconditional_conditioning=unconditional_conditioning, **kwargs)
+            return samples, None
+        if sampler_name == "dpmpp_2m":
+            # mask / x0 / eta travel on; eta != 0 raises in DPMSolverSampler.make_schedule, as for PLMS
+            if ddim_steps is None:
+                raise ValueError("sampler='dpmpp_2m' needs ddim_steps")
+            from .dpm_solver import DPMSolverSampler
+            samples, _ = DPMSolverSampler(self).sample(ddim_steps, batch_size, shape, cond, verbose=False,
+                                                       unconditional_guidance_scale=unconditional_guidance_scale, mask=mask,
+                                                       unconditional_conditioning=unconditional_conditioning, **kwargs)
             return samples, None
         if not ddim:
             kwargs.pop("eta", None)  # the ancestral sampler has no eta (the reference would raise here)
@@ -727,6 +752,7 @@ class LatentDiffusion(nn.Module):
         draws the posterior sample (one CPU randn of the latent shape, distributions.py:37-41) only to
         read its batch size; we replay the draw and skip the 345 GFLOP encode."""
         assert x_T is None
+        sampler = resolve_sampler(kwargs.get("sampler", None), use_plms)   # travels in **kwargs like `shard`
         if use_plms:
             assert ddim_steps is not None
         self.check_latent_t(self.latent_t_size)
@@ -782,7 +808,7 @@ class LatentDiffusion(nn.Module):
                                          ddim_steps=ddim_steps, eta=ddim_eta,
                                          unconditional_guidance_scale=unconditional_guidance_scale,
                                          unconditional_conditioning=unconditional_conditioning,
-                                         use_plms=use_plms)
+                                         use_plms=use_plms, **({} if sampler is None else {"sampler": sampler}))
         finally:
             self.noise_shard = None
         mel = self.decode_first_stage_cl(samples)  # [B, T, F, 1]
@@ -813,6 +839,7 @@ class LatentDiffusion(nn.Module):
         """ddpm.py:1573-1676 (inpainting / super-resolution): VAE-encode the given mel -> x0, keep the
         unmasked latent region (DDIM blends q_sample(x0, t) back in every step), regenerate the rest."""
         assert x_T is None
+        sampler = resolve_sampler(kwargs.get("sampler", None), use_plms)
         if use_plms:
             assert ddim_steps is not None
         self._check_candidates(n_gen, batch.get("text"))
@@ -846,7 +873,7 @@ class LatentDiffusion(nn.Module):
         samples, _ = self.sample_log(cond=c, batch_size=batch_size, x_T=x_T, ddim=use_ddim, ddim_steps=ddim_steps,
                                      eta=ddim_eta, unconditional_guidance_scale=unconditional_guidance_scale,
                                      unconditional_conditioning=unconditional_conditioning, use_plms=use_plms,
-                                     mask=mask, x0=torch.cat([z] * n_gen))
+                                     mask=mask, x0=torch.cat([z] * n_gen), **({} if sampler is None else {"sampler": sampler}))
         mel = self.decode_first_stage_cl(samples)
         waveform = self.mel_spectrogram_to_waveform(mel.view(mel.shape[0], mel.shape[1], mel.shape[2]),
                                                     savepath="", bs=None, name=batch.get("fname"), save=False)
@@ -969,15 +996,23 @@ def wav_to_fbank(source, target_length=1024, fn_STFT=None):
     return _pad_spec(fbank, target_length), _pad_spec(log_mag, target_length), waveform
 
 
+def _sampler_kwargs(sampler):
+    """What the two entry points add to generate_batch* for `sampler=`: nothing for None (today's call, unchanged); a named
+    sampler is deterministic, and these entry points have no eta parameter, so eta 0 goes with the name."""
+    return {} if resolve_sampler(sampler) is None else {"sampler": sampler, "ddim_eta": 0.0}
+
+
 def super_resolution_and_inpainting(latent_diffusion, text, transcription="", original_audio_file_path=None,
                                     seed=42, ddim_steps=200, duration=None, batchsize=1, guidance_scale=2.5,
                                     n_candidate_gen_per_text=3, time_mask_ratio_start_and_end=(0.40, 0.6),
                                     freq_mask_ratio_start_and_end=(1.0, 1.0), latent_t_per_second=25.6,
-                                    config=None):
-    """pipeline.py:213-267: same signature and defaults.  `original_audio_file_path` may also be a 1-D
+                                    config=None, sampler=None):
+    """pipeline.py:213-267: same signature and defaults, plus a trailing `sampler` (None: the reference's DDIM at eta 1;
+    "dpmpp_2m": DPM-Solver++(2M), deterministic, so ddim_eta=0.0 travels with it).  `original_audio_file_path` may also be a 1-D
     float waveform at 16 kHz.  STFT/mel (a17), VAE encode (a18), masked DDIM, decode and vocoder all run
     on the HIP path."""
     from .stft import TacotronSTFT
+    sampler_kw = _sampler_kwargs(sampler)
     seed_everything(int(seed))
     if config is not None:
         raise NotImplementedError("YAML configs are host glue of the reference; pass config=None")
@@ -990,7 +1025,7 @@ def super_resolution_and_inpainting(latent_diffusion, text, transcription="", or
             batch, unconditional_guidance_scale=guidance_scale, ddim_steps=ddim_steps,
             n_gen=n_candidate_gen_per_text, duration=duration,
             time_mask_ratio_start_and_end=time_mask_ratio_start_and_end,
-            freq_mask_ratio_start_and_end=freq_mask_ratio_start_and_end)
+            freq_mask_ratio_start_and_end=freq_mask_ratio_start_and_end, **sampler_kw)
 
 
 def save_wave(waveform, savepath, name="outwav", samplerate=16000):
@@ -1076,13 +1111,15 @@ def build_model(ckpt_path=None, config=None, device=None, model_name="audioldm2-
 
 def text_to_audio(latent_diffusion, text, transcription="", seed=42, ddim_steps=200, duration=10,
                   batchsize=1, guidance_scale=3.5, n_candidate_gen_per_text=3, latent_t_per_second=25.6,
-                  config=None):
+                  config=None, sampler=None):
     """pipeline.py:181-211: same signature, side effects (sets latent_t_size) and return value
-    (np.float32 [batchsize, 1, samples])."""
+    (np.float32 [batchsize, 1, samples]), plus a trailing `sampler` (None: the reference's DDIM at eta 1; "dpmpp_2m":
+    DPM-Solver++(2M) over `ddim_steps`, deterministic, so ddim_eta=0.0 travels with it)."""
+    sampler_kw = _sampler_kwargs(sampler)
     seed_everything(int(seed))
     batch = make_batch_for_text_to_audio(text, transcription=transcription, batchsize=batchsize)
     latent_diffusion.latent_t_size = int(duration * latent_t_per_second)
     with torch.no_grad():
         return latent_diffusion.generate_batch(batch, unconditional_guidance_scale=guidance_scale,
                                                ddim_steps=ddim_steps, n_gen=n_candidate_gen_per_text,
-                                               duration=duration)
+                                               duration=duration, **sampler_kw)

@@ -481,6 +481,15 @@ int aldm_plms_first_step(const float* x, const float* e_t, const float* e_next, 
                          float* pred_x0, float* hist, int64_t n, void* stream);
 int aldm_plms_step_indexed(float* x, const float* eps, float* hist, const float* coef_tab, const int* step_idx,
                            float* pred_x0, int64_t n, int coef_ld, void* stream);
+/* DPM-Solver++(2M), deterministic, data-prediction form (Lu et al. 2022, Algorithm 2; ABI v12), in place on x.  s = *step_idx,
+ * coef = coef_tab[s] (rows of coef_ld >= 7 floats) = {sigma_t, alpha_t, sigma_prev/sigma_t, -alpha_prev*expm1(-h), w, guidance_scale,
+ * use_cfg} with alpha = sqrt(abar), sigma = sqrt(1 - abar), h = lambda_prev - lambda_t, lambda = log(alpha/sigma), w = 1/(2r),
+ * r = h_last/h; w == 0 marks a first-order step.  eps holds [e_uncond ; e_cond] ([2, n]) when coef[6] != 0, else [1, n].
+ *   e = e_u + s*(e_c - e_u); x0 = (x - c0*e)/c1; D = x0 (w == 0) | x0 + w*(x0 - x0_buf); x = c2*x + c3*D; x0_buf = x0.
+ * x0_buf[n] is the one-slab history and the pred_x0 output; at w == 0 its old content is not read (it may be uninitialised).
+ * The counter is not range-checked, as in aldm_ddim_step_indexed: aldm_step_advance saturates it at the last row.           */
+int aldm_dpmpp_step_indexed(float* x, const float* eps, float* x0_buf, const float* coef_tab, const int* step_idx, int64_t n,
+                            int coef_ld, void* stream);
 /* *step_idx += 1 and t_cur[0..nt) = t_tab[min(*step_idx, steps-1)] (the next step's timestep row, the UNet's static input;
  * the time_range of ddim.py:205-213 stored as floats, one row per step in loop order)                                  */
 int aldm_step_advance(int* step_idx, const float* t_tab, float* t_cur, int nt, int steps, void* stream);
