@@ -1559,6 +1559,21 @@ extern "C" int aldm_attention_sched(int sched) {
     return g_attn_sched.load();
 }
 
+// Query tiles per wave of every attention launcher below: 2 = 64 queries per wave (every K / V fragment and its split reused for two
+// query tiles; a block owns 256 queries) whenever the grid still has >= 128 blocks: 1024x1024 self-attention 85.7 us vs 106 (QT = 1),
+// 256x256 (192 blocks) 14.7 vs 16.5 us, 1024x32 cross-attention 11.2 vs 13.2 us on MI355X (profiles/r02_attn_ab_pipelined.txt; round 1's
+// kernel preferred QT = 1 for short key lists).  Not for Lq < 128: with 64 queries per wave a 64-query launch keeps ONE wave of each
+// block busy — 16 x 20 heads x 64 x 64 in bf16x6: 13.0 us with 64 queries per wave, 8.0 us with 32 (profiles/r04_attn_probe_fp32_pv.txt).
+static int attention_query_tiles(int B, int heads, int Lq) {
+    static const int env_qt = [] {
+        const char* e = getenv("ALDM_ATTN_QT");  // A/B override: 1 or 2 query tiles per wave
+        return e ? atoi(e) : 0;
+    }();
+    const bool qt2 = env_qt ? env_qt == 2 : (Lq >= 128 && (int64_t)cdiv(Lq, 256) * heads * B >= 128);
+    return qt2 ? 2 : 1;
+}
+extern "C" int aldm_attention_query_tiles(int B, int heads, int Lq) { return attention_query_tiles(B, heads, Lq); }
+
 static int attention_launch(const float* q, const float* k, const float* v, float* out, void* out_split, int parts, int B,
                             int heads, int Lq, int Lk, int ldq, int ldk, int ldv, int ldo,
                             const float* mask, float scale, void* stream) {
@@ -1575,20 +1590,11 @@ static int attention_launch(const float* q, const float* k, const float* v, floa
                  reinterpret_cast<uintptr_t>(out)) & 15) == 0,
                "aldm_attention_d32: q/k/out must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    // 64 queries per wave (every K / V fragment and its split reused for two query tiles) whenever the grid still has >= 128
-    // blocks: 1024x1024 self-attention 85.7 us vs 106 (QT = 1), 256x256 (192 blocks) 14.7 vs 16.5 us, 1024x32 cross-attention
-    // 11.2 vs 13.2 us on MI355X (profiles/r02_attn_ab_pipelined.txt; round 1's kernel preferred QT = 1 for short key lists)
-    static const int env_qt = [] {
-        const char* e = getenv("ALDM_ATTN_QT");  // A/B override: 1 or 2 query tiles per wave
-        return e ? atoi(e) : 0;
-    }();
     static const bool pipe = [] {   // A/B override: ALDM_ATTN_PIPE=0 runs the phase-by-phase kernel on the bf16 paths too
         const char* e = getenv("ALDM_ATTN_PIPE");
         return e == nullptr || e[0] != '0';
     }();
-    // (not for Lq < 128: with 64 queries per wave a 64-query launch keeps ONE wave of each block busy — 16 x 20 heads x 64 x 64 in
-    //  bf16x6: 13.0 us with 64 queries per wave, 8.0 us with 32, profiles/r04_attn_probe_fp32_pv.txt)
-    const bool qt2 = env_qt ? env_qt == 2 : (Lq >= 128 && (int64_t)cdiv(Lq, 256) * heads * B >= 128);
+    const bool qt2 = attention_query_tiles(B, heads, Lq) == 2;
     const int gm = g_attn_mma.load();
     const int amode = gm < 0 ? default_attn_mode() : gm;
     dim3 grid(cdiv(Lq, qt2 ? 256 : 128), heads, B);
@@ -1637,13 +1643,7 @@ extern "C" int aldm_attention_d32_presplit(const float* q, const void* k_split, 
     ALDM_CHECK((amode == 3 && parts == 2) || (amode == 2 && parts == 3),
                "aldm_attention_d32_presplit: %d-part images need the %s attention mode (mode in force: %d)", parts,
                parts == 2 ? "bf16x3" : "bf16x6", amode);
-    static const int env_qt = [] {
-        const char* e = getenv("ALDM_ATTN_QT");
-        return e ? atoi(e) : 0;
-    }();
-    // (not for Lq < 128: with 64 queries per wave a 64-query launch keeps ONE wave of each block busy — 16 x 20 heads x 64 x 64 in
-    //  bf16x6: 13.0 us with 64 queries per wave, 8.0 us with 32, profiles/r04_attn_probe_fp32_pv.txt)
-    const bool qt2 = env_qt ? env_qt == 2 : (Lq >= 128 && (int64_t)cdiv(Lq, 256) * heads * B >= 128);
+    const bool qt2 = attention_query_tiles(B, heads, Lq) == 2;
     dim3 grid(cdiv(Lq, qt2 ? 256 : 128), heads, B);
     hipStream_t st = (hipStream_t)stream;
     const float* kf = reinterpret_cast<const float*>(k_split);
@@ -1741,11 +1741,7 @@ extern "C" int aldm_attention_d32_presplit_f16(const float* q, const void* k_spl
     ALDM_CHECK(((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k_split) | reinterpret_cast<uintptr_t>(vt_split) |
                  reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(out_split)) & 15) == 0,
                "aldm_attention_d32_presplit_f16: operands must be 16-byte aligned");
-    static const int env_qt = [] {
-        const char* e = getenv("ALDM_ATTN_QT");
-        return e ? atoi(e) : 0;
-    }();
-    const bool qt2 = env_qt ? env_qt == 2 : (Lq >= 128 && (int64_t)cdiv(Lq, 256) * heads * B >= 128);
+    const bool qt2 = attention_query_tiles(B, heads, Lq) == 2;
     dim3 grid(cdiv(Lq, qt2 ? 256 : 128), heads, B);
     hipStream_t st = (hipStream_t)stream;
     const float q_mul = scale * 1.44269504088896340736f * q_scale, sc_c = 1.0f / (q_scale * k_scale), out_mul = 1.0f / v_scale;

@@ -558,6 +558,12 @@ def attention_sched(sched: int) -> int:
     return _l.load().aldm_attention_sched(sched)
 
 
+def attention_query_tiles(B: int, heads: int, Lq: int) -> int:
+    """Query tiles per wave (1 or 2) every attention launcher picks for this shape (aldm_attention_query_tiles; host only): 2 is the
+    64-queries-per-wave kernel family, 256 queries per block."""
+    return _l.load().aldm_attention_query_tiles(B, heads, Lq)
+
+
 def debug_drop_product(on: bool) -> bool:
     """TEST HOOK (aldm_debug_drop_product): DMA-fed launches leave out the smallest of the six bf16 partial products — only the
     classic 64x128 / 2-stage tile has that instantiation, every other igemm launch fails while the switch is on.  Returns the

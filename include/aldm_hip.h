@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 /* ---- library / error ------------------------------------------------------------------ */
-int aldm_version(void);              /* ABI version (11), bumped on any struct / entry change */
+int aldm_version(void);              /* ABI version (13), bumped on any struct / entry change */
 const char* aldm_last_error(void);   /* message of the last failing call on this thread     */
 
 /* ---- activations usable as prologue (applied to the gathered input) or epilogue -------- */
@@ -360,6 +360,10 @@ int aldm_attention_mma(int mode);
  * reference per row (opt-in experiment, 1.7x the error), 3 = K / V^T tiles shared by a block's waves through LDS (ABI v9).
  * Returns the previous setting; other values only query.                                                                  */
 int aldm_attention_sched(int sched);
+/* Query tiles per wave (1 | 2) that every attention launcher above picks for this (B, heads, Lq) (ABI v13; host only, no launch):
+ * 2 = 64 queries per wave and 256 per block, taken when Lq >= 128 and ceil(Lq / 256) * heads * B >= 128; $ALDM_ATTN_QT (read
+ * once) overrides.  For tests, which reach either kernel family by shape and assert here which one they reached.          */
+int aldm_attention_query_tiles(int B, int heads, int Lq);
 /* "f16x3" self-attention (ABI v9): k_split / vt_split are the 2-part fp16 images an ALDM_EPI_QKV launch with out_split_fmt =
  * ALDM_FMT_F16 wrote (of k_scale * k and v_scale * v); q is split in the kernel into fp16 parts of q_scale * scale * log2(e) * q
  * (the caller vouches for |q_scale * scale * log2(e) * q| <= 65504: a LayerNorm-fed projection is bounded by R c), the

@@ -137,6 +137,17 @@ def test_every_tuned_dma_table_entry_plans_onto_the_hinted_kernel():
     assert n >= 300
 
 
+def test_attention_query_tiles_rule():
+    """aldm_attention_query_tiles (host only): the one rule by which every attention launcher picks 32 or 64 queries per wave —
+    64 (two query tiles) when Lq >= 128 and the grid of 256-query blocks still has ceil(Lq / 256) * heads * B >= 128 of them.
+    ($ALDM_ATTN_QT, read once per process, overrides the rule: this table is the rule's, with the variable unset.)"""
+    from audioldm2_amd import ops
+    assert "ALDM_ATTN_QT" not in os.environ, "ALDM_ATTN_QT pins the kernel family: unset it to test the rule"
+    for B, heads, Lq, tiles in ((16, 8, 1024, 2), (2, 8, 1024, 1), (16, 8, 64, 1), (16, 8, 127, 1), (16, 8, 128, 2), (8, 8, 256, 1),
+                                (8, 8, 257, 2), (16, 20, 64, 1)):
+        assert ops.attention_query_tiles(B, heads, Lq) == tiles, (B, heads, Lq)
+
+
 def test_missing_library_fails_loudly(tmp_path, monkeypatch):
     from audioldm2_amd import lib
     monkeypatch.setattr(lib, "_lib", None)

@@ -40,6 +40,16 @@ profiles/r07_f16x3_outlier_errors.txt; the bars are the fp32-grade ones above, "
   LayerNorm -> GEGLU -> FF-out, gate / value row x 2^4 .. 2^12    3.9e-7 .. 1.9e-6 / 4.4e-7 .. 9.1e-7   (<= 1.1e-6 / 7.6e-7)   5e-6
     ... one gate row x 2^8 under the former (R c + b)^2 bound     1.1e-6 / 3.4e-5 (fails the sub-block assert alone)           5e-6
   LayerNorm -> QKV -> attention -> to_out, W_v / W_k column, row  5.6e-7 .. 5.8e-6 / 5.5e-7 .. 1.4e-6   (<= 7.0e-6 / 2.2e-6)   5e-6 (+ 2^-24 max|score| log2 e with W_k)
+
+The 64-queries-per-wave attention kernels at ragged lengths, against fp64 (tests/test_attention_qt2_gpu.py,
+profiles/r11_attention_qt2_errors.txt; the bars are fused_tol's, set before these kernels were measured on their own):
+
+  quantity                                                        measured (typical .. worst)            bar
+  fp32-K/V kernels, ragged Lq / Lk, masks: f32 | bf16x6           3.1e-7 .. 6.4e-7 | 2.5e-7 .. 4.5e-7    5e-6
+  ... bf16x3                                                      5.8e-6 .. 1.4e-5                       5e-5
+  pre-split TAIL self-attention behind its QKV projection         bf16x6 1.0e-6 .. 1.5e-6                5e-6
+  ... bf16x3 | f16x3 (LayerNorm-fed)                              1.2e-5 .. 1.4e-5 | 6.6e-7 .. 8.8e-7    5e-5 | 5e-6
+  pre-split schedules 1 / 2 at partial query blocks               bf16x6 4.5e-7 / 4.1e-7, bf16x3 7.6e-6 / 8.4e-6   5e-6, 5e-5 (+ _score_tol for 2)
 """
 import os
 
