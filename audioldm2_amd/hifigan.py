@@ -123,7 +123,7 @@ class Generator(nn.Module):
             Lout = (L - 1) * u - 2 * p + k
             phases = pk["ups"][i]
             Tt = phases[0].KW
-            y = torch.empty((B, 1, Lout, phases[0].N), device=x.device, dtype=torch.float32)
+            y = torch.empty((B, 1, Lout, phases[0].N), device=x.device, dtype=x.dtype)
             Q = (Lout + p) // u + 2
             for ph in range(u):
                 ops.conv(x, phases[ph], pad=(0, Tt - 1), out_hw=(1, Q), pre_act=ACT_LRELU,
@@ -169,7 +169,7 @@ class Generator(nn.Module):
         Lout = (L - 1) * u - 2 * p + k
         phases = pk["ups"][i]
         Tt = phases[0].KW
-        y = torch.empty((B, 1, Lout, phases[0].N), device=x.device, dtype=torch.float32)
+        y = torch.empty((B, 1, Lout, phases[0].N), device=x.device, dtype=x.dtype)
         Q = (Lout + p) // u + 2
         xa = ops.split_rows(x, act=ACT_LRELU, slope=LRELU_SLOPE)
         for ph in range(u):

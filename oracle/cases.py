@@ -73,6 +73,11 @@ HIFIGAN_48K = dict(upsample_rates=[6, 5, 4, 2, 2], upsample_kernel_sizes=[12, 10
                    upsample_initial_channel=1536, resblock_kernel_sizes=[3, 7, 11, 15],
                    resblock_dilation_sizes=[[1, 3, 5], [1, 3, 5], [1, 3, 5], [1, 3, 5]], num_mels=256,
                    resblock="1")
+# Two stages of the 48 kHz generator in small (tests/test_vocoder_dma_gpu.py, tests/test_host_logic.py): 384 -> 192 channels (the
+# 48 kHz generator's third stage: at least 128, so it runs on pre-split operands) and 192 -> 96 (the register-staged form).
+HIFIGAN_2STAGE = dict(upsample_rates=[4, 2], upsample_kernel_sizes=[8, 4], upsample_initial_channel=384,
+                      resblock_kernel_sizes=[3, 7, 11, 15],
+                      resblock_dilation_sizes=[[1, 3, 5], [1, 3, 5], [1, 3, 5], [1, 3, 5]], num_mels=64, resblock="1")
 
 
 def latent_input(B, C, H, W, seed=0):

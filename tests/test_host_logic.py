@@ -556,6 +556,131 @@ def test_t5_and_phoneme_host_logic_match_reference_fixtures(monkeypatch):
     assert float((emb - wantp).abs().max() / wantp.abs().max()) < 1e-5 and np.array_equal(pm.numpy(), gp["mask"])
 
 
+def _torch_ops_stand_in_hifigan(dma, calls):
+    """Torch (CPU) stand-ins for the ops audioldm2_amd/hifigan.py calls — TEST ONLY, like `_torch_ops_stand_in`: every launch form
+    of ops.conv the vocoder uses (padding, dilation, explicit output length, the polyphase row remap, operand / result / image
+    activations, residual, alpha, out / accumulate, both split_out forms) restated with F.conv1d in the operand's own dtype, the
+    polyphase packing as a per-phase slice of the transposed-conv weight, and a `SplitT` that just carries the tensor.  The
+    epilogue order is the engine's: v = act(conv + bias); v = alpha * (v + res); out = accumulate ? out + v : v; the image holds
+    split_act(out).  `calls` counts the launches by kind."""
+    import types
+    import torch.nn.functional as F
+    from audioldm2_amd.lib import ACT_LRELU, ACT_NONE, ACT_TANH
+
+    class PW:
+        def __init__(self, w, b):          # w [N, Cin, KW] as F.conv1d takes it
+            self.w, self.b = w.detach(), None if b is None else b.detach()
+            self.N, self.Cin, self.KH, self.KW = w.shape[0], w.shape[1], 1, w.shape[2]
+
+    class SplitT:
+        def __init__(self, t):
+            self.t, self.shape = t, tuple(t.shape)
+
+    def act_of(v, act, slope):
+        if act == ACT_LRELU:
+            return torch.where(v > 0, v, v * slope)
+        if act == ACT_TANH:
+            return torch.tanh(v)
+        assert act == ACT_NONE, act
+        return v
+
+    def pack_convtr1d(weight, bias, stride):
+        """Phase ph of ConvTranspose1d [Cin, N, K] is a stride-1 conv over taps kk = ph + j * stride, j = 0 .. T - 1 (zero past K),
+        input position q - j: as a correlation, tap kw = T - 1 - j behind a left padding of T - 1."""
+        Cin, N, K = weight.shape
+        T = (K + stride - 1) // stride
+        out = []
+        for ph in range(stride):
+            w = weight.new_zeros(N, Cin, T)
+            for j in range(T):
+                if ph + j * stride < K:
+                    w[:, :, T - 1 - j] = weight[:, :, ph + j * stride].t()
+            out.append(PW(w, bias))
+        return out
+
+    def split_rows(x, act=ACT_NONE, slope=0.0):
+        calls["split_rows"] += 1
+        return SplitT(act_of(x, act, slope))
+
+    def conv(x, pw, *, pad=(0, 0), dil=(1, 1), out_hw=None, remap=None, pre_act=ACT_NONE, pre_slope=0.0, act=ACT_NONE,
+             act_slope=0.0, res=None, alpha=1.0, out=None, accumulate=False, split_out=None, split_act=ACT_NONE, split_slope=0.0):
+        if isinstance(x, SplitT):
+            assert pre_act == ACT_NONE, "a pre-split operand takes no prologue"
+            calls["conv_split"] += 1
+            a = x.t
+        else:
+            calls["conv_fp32"] += 1
+            a = act_of(x, pre_act, pre_slope)
+        B, H, W, C = a.shape
+        assert H == 1 and C == pw.Cin and pad[0] == 0 and dil[0] == 1
+        OW = W + 2 * pad[1] - dil[1] * (pw.KW - 1) if out_hw is None else out_hw[1]
+        right = OW - 1 + dil[1] * (pw.KW - 1) - pad[1] - (W - 1)      # zeros past the last input row the last output reads
+        v = F.conv1d(F.pad(a[:, 0].transpose(1, 2), (pad[1], right)), pw.w, pw.b, dilation=dil[1]).transpose(1, 2)
+        assert v.shape == (B, OW, pw.N)
+        v = act_of(v, act, act_slope)
+        if remap is None:
+            rows = torch.arange(OW)
+            oshape = (B, 1, OW, pw.N)
+        else:
+            mul, off, out_len = remap
+            rows = torch.arange(OW) * mul + off
+            keep = (rows >= 0) & (rows < out_len)
+            v, rows = v[:, keep], rows[keep]
+            oshape = (B, 1, out_len, pw.N)
+        if res is not None:
+            v = v + res.view(B, oshape[2], pw.N)[:, rows]
+        v = v * alpha
+        if split_out == "only":
+            assert out is None and not accumulate and remap is None
+        elif out is None:
+            assert not accumulate
+            out = torch.full(oshape, float("nan"), dtype=v.dtype)
+        if out is not None:
+            o = out.view(B, oshape[2], pw.N)
+            o[:, rows] = o[:, rows] + v if accumulate else v
+            v = o[:, rows]
+        if split_out is None:
+            return out.view(oshape)
+        assert remap is None
+        img = SplitT(act_of(v, split_act, split_slope).view(oshape))
+        return img if split_out == "only" else (out.view(oshape), img)
+
+    return types.SimpleNamespace(
+        ACT_LRELU=ACT_LRELU, ACT_TANH=ACT_TANH, SplitT=SplitT, pack_conv=lambda w, b=None: PW(w, b), pack_convtr1d=pack_convtr1d,
+        split_rows=split_rows, conv=conv, use_dma=lambda: dma, nchw_to_nhwc=lambda x: x.permute(0, 2, 3, 1).contiguous())
+
+
+@pytest.mark.parametrize("dma,dma_min,dma_stages", [(True, 128, 1), (True, 32, 2), (False, 128, 0)])
+def test_hifigan_stage_wiring_matches_the_oracle_in_both_stage_forms(monkeypatch, dma, dma_min, dma_stages):
+    """audioldm2_amd.hifigan.Generator with the device ops replaced by torch stand-ins, in fp64 on the CPU, against
+    oracle.vae.hifigan_forward: the pre-split stage (`_stage_dma`: one leaky-relu image shared by the ResBlocks, the (r, rl) pairs
+    handed from conv2 to the next conv1, alpha = 1 / num_kernels with accumulate = (j > 0), the polyphase offsets) and the
+    register-staged stage compute the reference's generator to rounding — the wiring, independently of any kernel
+    (tests/test_vocoder_dma_gpu.py has those).  Two stages, 192 and 96 output channels: with the threshold at 128 the first takes
+    the pre-split form and the second the register-staged one; at 32 both take it; with ops.use_dma() off neither."""
+    from audioldm2_amd import hifigan
+    from oracle import cases, weights
+    from oracle.vae import hifigan_forward
+    hc = cases.HIFIGAN_2STAGE
+    calls = {"split_rows": 0, "conv_split": 0, "conv_fp32": 0}
+    monkeypatch.setattr(hifigan, "ops", _torch_ops_stand_in_hifigan(dma, calls))
+    monkeypatch.setattr(hifigan.Generator, "DMA_MIN_CHANNELS", dma_min)
+    gen = hifigan.Generator(dict(hc))
+    sd = weights.make_state_dict(weights.shapes_of(gen), seed=11)
+    gen.load_state_dict(sd, strict=True)
+    gen = gen.double()
+    mel = cases.mel_input(2, hc["num_mels"], 37, seed=3).double()
+    want = hifigan_forward({k: v.double() for k, v in sd.items()}, hc, mel)
+    got = gen.forward_cl(mel.transpose(1, 2).contiguous())
+    assert got.dtype == torch.float64 and got.shape == want.shape == (2, 1, 37 * 8)
+    assert float((got - want).abs().max() / want.abs().max()) < 1e-12
+    nk, rates = len(hc["resblock_kernel_sizes"]), hc["upsample_rates"]
+    per_stage = [u + nk * 6 for u in rates]                       # polyphase launches + (conv1, conv2) x 3 dilations per ResBlock
+    assert calls["split_rows"] == 2 * dma_stages                  # the upsampler's operand and the ResBlocks' shared image
+    assert calls["conv_split"] == sum(per_stage[:dma_stages])
+    assert calls["conv_fp32"] == sum(per_stage[dma_stages:]) + 2  # + conv_pre, conv_post
+
+
 def test_retarget_config_maps_the_reference_configs_onto_the_hip_targets(tmp_path):
     """pipeline.retarget_config / build_model(config=<yaml path>) (pipeline.py:155-157): the reference's own config dicts
     (utils.py:116-561), as dicts and through a YAML file, come out with our targets and untouched params — and equal the

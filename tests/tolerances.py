@@ -50,6 +50,18 @@ profiles/r11_attention_qt2_errors.txt; the bars are fused_tol's, set before thes
   pre-split TAIL self-attention behind its QKV projection         bf16x6 1.0e-6 .. 1.5e-6                5e-6
   ... bf16x3 | f16x3 (LayerNorm-fed)                              1.2e-5 .. 1.4e-5 | 6.6e-7 .. 8.8e-7    5e-5 | 5e-6
   pre-split schedules 1 / 2 at partial query blocks               bf16x6 4.5e-7 / 4.1e-7, bf16x3 7.6e-6 / 8.4e-6   5e-6, 5e-5 (+ _score_tol for 2)
+
+The launch forms of the vocoder's pre-split stage (hifigan.py Generator._stage_dma), against fp64 (tests/test_vocoder_dma_gpu.py,
+profiles/r12_vocoder_dma_errors.txt; two samples of 203 rows, 128 / 192 channels, the planner's tile and forced 64- / 128- / 256-row
+tiles without and with split-K 3; the bars are gemm_tol's and tail_tol's, set before these launches were measured on their own):
+
+  quantity                                                        measured bf16x6 (typical .. worst)   bar    measured bf16x3      bar
+  conv1: dilated conv on the leaky-relu image, leaky-relu epilogue  4.3e-7 .. 5.8e-7                   2e-6   3.0e-6 .. 3.7e-6     5e-5
+  conv2 + residual, image of leaky_relu(result)                   3.5e-7 .. 5.6e-7                     2e-6   2.3e-6 .. 2.8e-6     5e-5
+  closing launches: alpha = 1/3, out=, accumulate (one / three)   3.6e-7 .. 6.2e-7 / 3.1e-7 .. 4.2e-7  2e-6   2.8e-6 .. 3.0e-6     5e-5
+  polyphase transposed conv on a pre-split operand, row remap     3.9e-7 .. 7.9e-7                     2e-6   3.3e-6 .. 3.6e-6     5e-5
+  two-stage generator vs the fp64 oracle: stage 0 pre-split       2.3e-6 (f16x3: the same launches)    4e-5   2.4e-5               2e-4
+  ... everything register-staged | torch fp32 on the CPU          2.9e-6 | 2.8e-6                      4e-5   2.9e-6 (six products)
 """
 import os
 
