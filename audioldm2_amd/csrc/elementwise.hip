@@ -259,6 +259,125 @@ __global__ void dpmpp_step_indexed_vec4_kernel(float* __restrict__ x, const floa
     }
 }
 
+// ---- guidance rescale (Lin et al. 2023, "Common Diffusion Noise Schedules and Sample Steps are Flawed", section 3.4) -------------
+// Row s = *step_idx (row 0 without a counter) of coef_tab: column 5 = guidance scale, column 7 = phi.  Per sample b of eps[2, B, n_s]:
+//   e_g = e_u + s (e_c - e_u);  f = phi std(e_c) / std(e_g) + (1 - phi);  out = f e_g      (f = 1 when std(e_g) == 0 or n_s == 1)
+// One workgroup of 1024 threads per sample, three sweeps over the sample's two slabs (the second and third come from L2): the
+// means, then the sums of squared deviations from them (two-pass: E[x^2] - E[x]^2 loses the digits the mean takes), then the
+// apply.  e_g is the same expression in every sweep.  Each thread accumulates its strided elements in order, a wave reduces by
+// shuffles, the 16 wave partials go through LDS and EVERY thread adds them in slot order: a fixed order, no atomics, no flags,
+// and one f for the whole workgroup.  A NaN or Inf in a sample reaches its statistics and so all of that sample's outputs.
+constexpr int kRescaleThreads = 1024;
+
+// (a, b) summed over the workgroup, the totals returned in every thread; sm: one slot per wave
+__device__ __forceinline__ void rescale_block_sum2(float& a, float& b, float (*sm)[2]) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        a += __shfl_xor(a, o);
+        b += __shfl_xor(b, o);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        sm[threadIdx.x >> 6][0] = a;
+        sm[threadIdx.x >> 6][1] = b;
+    }
+    __syncthreads();
+    a = 0.f;
+    b = 0.f;
+#pragma unroll
+    for (int w = 0; w < kRescaleThreads / 64; ++w) {
+        a += sm[w][0];
+        b += sm[w][1];
+    }
+    __syncthreads();   // the slots are free for the next reduction
+}
+
+template <int W>
+__device__ __forceinline__ void rescale_load(const float* __restrict__ p, float (&v)[W]) {
+    if constexpr (W == 4) {
+        const f32x4 q = *reinterpret_cast<const f32x4*>(p);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = q[k];
+    } else {
+        v[0] = *p;
+    }
+}
+
+// W floats per lane and access: 4 for n_s % 4 == 0 and 16-byte aligned eps / out (every sample's slabs are aligned then), else 1
+template <int W>
+__global__ __launch_bounds__(kRescaleThreads) void cfg_rescale_indexed_kernel(const float* __restrict__ eps, float* __restrict__ out,
+                                                                              const float* __restrict__ coef_tab,
+                                                                              const int* __restrict__ step_idx, int B, int64_t n_s,
+                                                                              int coef_ld) {
+    __shared__ float sm[kRescaleThreads / 64][2];
+    const float* coef = coef_tab + (step_idx ? (int64_t)*step_idx : 0) * coef_ld;
+    const float gs = coef[5], phi = coef[7];
+    const int64_t b = blockIdx.x;
+    const float* eu = eps + b * n_s;
+    const float* ec = eps + (B + b) * n_s;
+    float* o = out + b * n_s;
+    const int64_t nv = n_s / W;
+    const float n = (float)n_s;
+
+    // W accumulators per thread and statistic (one per element of an access), added in element order after the sweep
+    float pc[W] = {}, pg[W] = {};
+    for (int64_t i = threadIdx.x; i < nv; i += kRescaleThreads) {
+        float u[W], c[W];
+        rescale_load<W>(eu + i * W, u);
+        rescale_load<W>(ec + i * W, c);
+#pragma unroll
+        for (int k = 0; k < W; ++k) {
+            pc[k] += c[k];
+            pg[k] += u[k] + gs * (c[k] - u[k]);
+        }
+    }
+    float sc = pc[0], sg = pg[0];
+#pragma unroll
+    for (int k = 1; k < W; ++k) {
+        sc += pc[k];
+        sg += pg[k];
+    }
+    rescale_block_sum2(sc, sg, sm);
+    const float mc = sc / n, mg = sg / n;
+
+#pragma unroll
+    for (int k = 0; k < W; ++k) pc[k] = pg[k] = 0.f;
+    for (int64_t i = threadIdx.x; i < nv; i += kRescaleThreads) {
+        float u[W], c[W];
+        rescale_load<W>(eu + i * W, u);
+        rescale_load<W>(ec + i * W, c);
+#pragma unroll
+        for (int k = 0; k < W; ++k) {
+            const float dc = c[k] - mc;
+            const float dg = (u[k] + gs * (c[k] - u[k])) - mg;
+            pc[k] += dc * dc;
+            pg[k] += dg * dg;
+        }
+    }
+    float qc = pc[0], qg = pg[0];
+#pragma unroll
+    for (int k = 1; k < W; ++k) {
+        qc += pc[k];
+        qg += pg[k];
+    }
+    rescale_block_sum2(qc, qg, sm);
+    // std(e_c) / std(e_g): the 1 / n (or 1 / (n - 1)) of both cancels
+    const float f = (qg == 0.f || n_s == 1) ? 1.0f : phi * (sqrtf(qc) / sqrtf(qg)) + (1.0f - phi);
+
+    for (int64_t i = threadIdx.x; i < nv; i += kRescaleThreads) {
+        float u[W], c[W];
+        rescale_load<W>(eu + i * W, u);
+        rescale_load<W>(ec + i * W, c);
+        if constexpr (W == 4) {
+            f32x4 r;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) r[k] = f * (u[k] + gs * (c[k] - u[k]));
+            *reinterpret_cast<f32x4*>(o + i * 4) = r;
+        } else {
+            o[i] = f * (u[0] + gs * (c[0] - u[0]));
+        }
+    }
+}
+
 // last node of the step graph: counter += 1 and the NEXT step's timestep row into the UNet's static input (one block: every
 // thread reads the old counter before thread 0 stores the new one)
 __global__ void step_advance_kernel(int* __restrict__ step_idx, const float* __restrict__ t_tab, float* __restrict__ t_cur,
@@ -426,6 +545,25 @@ extern "C" int aldm_dpmpp_step_indexed(float* x, const float* eps, float* x0_buf
         hipLaunchKernelGGL(dpmpp_step_indexed_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, x, eps, x0_buf,
                            coef_tab, step_idx, n, coef_ld);
     ALDM_LAUNCH_CHECK("aldm_dpmpp_step_indexed");
+    return 0;
+}
+
+extern "C" int aldm_cfg_rescale_indexed(const float* eps, float* out, const float* coef_tab, const int* step_idx, int B, int64_t n_s,
+                                        int coef_ld, void* stream) {
+    ALDM_CHECK(eps && out && coef_tab, "aldm_cfg_rescale_indexed: null pointer");
+    ALDM_CHECK(B > 0 && B <= 65535 && n_s > 0 && n_s <= (1ll << 40), "aldm_cfg_rescale_indexed: bad args (B=%d, n_s=%lld)", B,
+               (long long)n_s);
+    ALDM_CHECK(coef_ld >= 8, "aldm_cfg_rescale_indexed: coef_ld=%d: rows of >= 8 floats (column 5 the scale, column 7 phi)", coef_ld);
+    const int64_t n = (int64_t)B * n_s;
+    ALDM_CHECK(out + n <= eps || eps + 2 * n <= out, "aldm_cfg_rescale_indexed: out overlaps eps");
+    const bool vec = n_s % 4 == 0 && (((uintptr_t)eps | (uintptr_t)out) & 15) == 0;
+    if (vec)
+        hipLaunchKernelGGL(cfg_rescale_indexed_kernel<4>, dim3((unsigned)B), dim3(kRescaleThreads), 0, (hipStream_t)stream, eps, out,
+                           coef_tab, step_idx, B, n_s, coef_ld);
+    else
+        hipLaunchKernelGGL(cfg_rescale_indexed_kernel<1>, dim3((unsigned)B), dim3(kRescaleThreads), 0, (hipStream_t)stream, eps, out,
+                           coef_tab, step_idx, B, n_s, coef_ld);
+    ALDM_LAUNCH_CHECK("aldm_cfg_rescale_indexed");
     return 0;
 }
 

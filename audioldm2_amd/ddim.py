@@ -265,6 +265,31 @@ def host_drawer(shape, noise_shard=None):
     return draw
 
 
+def check_guidance_rescale(phi) -> float:
+    """The `guidance_rescale` argument of the samplers and the pipeline as a float: phi of Lin et al. 2023 (section 3.4), in [0, 1];
+    0 is off."""
+    try:
+        phi = float(phi)
+    except (TypeError, ValueError):
+        raise ValueError(f"guidance_rescale must be a number in [0, 1], got {phi!r}")
+    if not (np.isfinite(phi) and 0.0 <= phi <= 1.0):
+        raise ValueError(f"guidance_rescale must be finite and in [0, 1], got {phi!r}")
+    return phi
+
+
+def guidance_table(rows, scale, use_cfg, phi=0.0):
+    """Pure host function: a sampler's [S, 8] fp32 coefficient table from its [S, 5] rows.  Column 5 = the guidance scale; column
+    6 = 1 when the step kernel combines eps[2, n] itself; column 7 = phi.  With guidance rescale on (guidance and phi > 0) the
+    combine moves into ops.cfg_rescale_indexed, which reads columns 5 and 7, and the step kernel gets a combined eps[n]: column 6 = 0."""
+    rescale = bool(use_cfg) and phi > 0.0
+    coef = torch.zeros(rows.shape[0], 8)
+    coef[:, :5] = rows
+    coef[:, 5] = float(scale)
+    coef[:, 6] = 1.0 if use_cfg and not rescale else 0.0
+    coef[:, 7] = float(phi) if rescale else 0.0
+    return coef
+
+
 class DDIMSampler(object):
     def __init__(self, model, schedule="linear", device=torch.device("cuda"), **kwargs):
         super().__init__()
@@ -308,8 +333,9 @@ class DDIMSampler(object):
                img_callback=None, quantize_x0=False, eta=0.0, mask=None, x0=None, temperature=1.0,
                noise_dropout=0.0, score_corrector=None, corrector_kwargs=None, verbose=True, x_T=None,
                log_every_t=100, unconditional_guidance_scale=1.0, unconditional_conditioning=None,
-               dynamic_threshold=None, ucg_schedule=None, **kwargs):
-        """ddim.py:94-163"""
+               dynamic_threshold=None, ucg_schedule=None, guidance_rescale=0.0, **kwargs):
+        """ddim.py:94-163, plus `guidance_rescale` (phi of Lin et al. 2023; 0: off — the reference's step)"""
+        guidance_rescale = check_guidance_rescale(guidance_rescale)
         if quantize_x0 or score_corrector is not None or dynamic_threshold is not None \
                 or noise_dropout != 0.0 or ucg_schedule is not None:
             raise NotImplementedError("DDIMSampler(HIP): option not used by the AudioLDM2 pipeline")
@@ -320,7 +346,7 @@ class DDIMSampler(object):
                                   mask=mask, x0=x0, temperature=temperature, x_T=x_T,
                                   log_every_t=log_every_t,
                                   unconditional_guidance_scale=unconditional_guidance_scale,
-                                  unconditional_conditioning=unconditional_conditioning)
+                                  unconditional_conditioning=unconditional_conditioning, guidance_rescale=guidance_rescale)
 
     # ------------------------------------------------------------------------------------------
     def _drawer(self, shape):
@@ -346,8 +372,9 @@ class DDIMSampler(object):
                       timesteps=None, quantize_denoised=False, mask=None, x0=None, img_callback=None,
                       log_every_t=100, temperature=1.0, noise_dropout=0.0, score_corrector=None,
                       corrector_kwargs=None, unconditional_guidance_scale=1.0,
-                      unconditional_conditioning=None, dynamic_threshold=None, ucg_schedule=None):
+                      unconditional_conditioning=None, dynamic_threshold=None, ucg_schedule=None, guidance_rescale=0.0):
         """ddim.py:166-262"""
+        guidance_rescale = check_guidance_rescale(guidance_rescale)
         if ddim_use_original_steps:
             # the reference's own p_sample_ddim reads `self.model.ddim_sigmas_for_original_num_steps` here (ddim.py:324-327), a
             # buffer it registered on the SAMPLER (ddim.py:84-91): with LatentDiffusion as the model this path raises
@@ -376,11 +403,9 @@ class DDIMSampler(object):
         img = img_h.to(dev).contiguous()
         # device tables in loop order (i = 0 is the noisiest step, index = total_steps - 1)
         order = [total_steps - i - 1 for i in range(total_steps)]
-        coef = torch.zeros(total_steps, 8)
-        coef[:, :5] = self.ddim_coef[order]
-        coef[:, 5] = float(unconditional_guidance_scale)
-        coef[:, 6] = 1.0 if use_cfg else 0.0
-        coef = coef.to(dev)
+        # guidance rescale: the combine and the per-sample rescale run in a launch of their own in front of the step kernel
+        rescale = use_cfg and guidance_rescale > 0.0
+        coef = guidance_table(self.ddim_coef[order], unconditional_guidance_scale, use_cfg, guidance_rescale).to(dev)
         nrep = 2 if use_cfg else 1
         t_tab = torch.from_numpy(np.ascontiguousarray(time_range)).float()[:, None].repeat(1, nrep * b).to(dev).contiguous()
 
@@ -410,8 +435,9 @@ class DDIMSampler(object):
                      and os.environ.get("ALDM_NO_GRAPH_CACHE", "0") != "1")
         key = None
         if can_cache:
+            # `rescale`: the launch sequence differs; the VALUES of the scale and phi live in coef_all, copied in below
             key = (tuple(shape), total_steps, tuple(tuple(c.shape) for c in prepared["ctxs"]),
-                   None if prepared["y"] is None else tuple(prepared["y"].shape))
+                   None if prepared["y"] is None else tuple(prepared["y"].shape), rescale)
         ent = unet._graph_cache.get(key) if can_cache else None
         if ent is not None and ent.get("kv") is None:
             # the entry never got as far as recording the K/V buffers its graph reads (e.g. an interrupted first run)
@@ -433,6 +459,8 @@ class DDIMSampler(object):
                    "step_idx": torch.zeros(1, device=dev, dtype=torch.int32), "coef_all": coef.clone(), "t_tab": t_tab.clone(),
                    "noise_all": torch.empty((total_steps,) + tuple(shape), device=dev, dtype=torch.float32),
                    "prepared": prepared}
+            if rescale:
+                ent["eps_g"] = torch.empty_like(img)   # the rescaled combined model output
 
             def step(e=ent):
                 x_c = e["x_cur"]
@@ -447,6 +475,8 @@ class DDIMSampler(object):
                         eps = torch.stack([e_u, e_c]).contiguous()
                 else:
                     eps = self.model.apply_model(x_c, e["t_cur"][:b].long(), cond).contiguous()
+                if rescale:
+                    eps = ops.cfg_rescale_indexed(eps, e["eps_g"], e["coef_all"], e["step_idx"])
                 ops.ddim_step_indexed(x_c, eps, e["noise_all"], e["coef_all"], e["step_idx"], e["pred_x0"])
                 ops.step_advance(e["step_idx"], e["t_tab"], e["t_cur"])
             ent["run_step"] = GraphStepper(step, self.use_graph)
@@ -499,9 +529,10 @@ class DDIMSampler(object):
     def p_sample_ddim(self, x, c, t, index, repeat_noise=False, use_original_steps=False,
                       quantize_denoised=False, temperature=1.0, noise_dropout=0.0, score_corrector=None,
                       corrector_kwargs=None, unconditional_guidance_scale=1.0,
-                      unconditional_conditioning=None, dynamic_threshold=None):
+                      unconditional_conditioning=None, dynamic_threshold=None, guidance_rescale=0.0):
         """ddim.py:265-355 — single step with the reference's signature (noise from the host CPU
-        generator, like `noise_like` does on a CPU reference run)."""
+        generator, like `noise_like` does on a CPU reference run), plus `guidance_rescale`."""
+        guidance_rescale = check_guidance_rescale(guidance_rescale)
         b = x.shape[0]
         use_cfg = not (unconditional_conditioning is None or unconditional_guidance_scale == 1.0)
         if use_cfg:
@@ -512,10 +543,10 @@ class DDIMSampler(object):
                                    self.model.apply_model(x, t, c)]).contiguous()
         else:
             eps = self.model.apply_model(x, t, c).contiguous()
-        coef = torch.zeros(8)
-        coef[:5] = self.ddim_coef[index]
-        coef[5] = float(unconditional_guidance_scale)
-        coef[6] = 1.0 if use_cfg else 0.0
+        coef = guidance_table(self.ddim_coef[index].reshape(1, 5), unconditional_guidance_scale, use_cfg, guidance_rescale)
+        if use_cfg and guidance_rescale > 0.0:
+            eps = ops.cfg_rescale_indexed(eps, torch.empty_like(eps[0]), coef.to(x.device))
+        coef = coef[0]
         if repeat_noise:
             noise = torch.randn((1, *x.shape[1:])).repeat(b, 1, 1, 1)
         else:
@@ -542,7 +573,7 @@ class DDIMSampler(object):
 
     @torch.no_grad()
     def decode(self, x_latent, cond, t_start, unconditional_guidance_scale=1.0, unconditional_conditioning=None,
-               use_original_steps=False, callback=None):
+               use_original_steps=False, callback=None, guidance_rescale=0.0):
         """ddim.py:452-491: run the last `t_start` DDIM steps from x_latent (one p_sample_ddim per step: the eager path over
         the same kernels as ddim_sampling; the step noise comes from the host generator in the reference's order)."""
         if use_original_steps:
@@ -557,7 +588,8 @@ class DDIMSampler(object):
             ts = torch.full((x_latent.shape[0],), int(step), device=x_latent.device, dtype=torch.long)
             x_dec, _ = self.p_sample_ddim(x_dec, cond, ts, index=index, use_original_steps=use_original_steps,
                                           unconditional_guidance_scale=unconditional_guidance_scale,
-                                          unconditional_conditioning=unconditional_conditioning)
+                                          unconditional_conditioning=unconditional_conditioning,
+                                          guidance_rescale=guidance_rescale)
             if callback:
                 callback(i)
         return x_dec

@@ -35,7 +35,8 @@ import numpy as np
 import torch
 
 from . import ops
-from .ddim import GraphStepper, host_drawer, make_ddim_sampling_parameters, make_ddim_timesteps
+from .ddim import (GraphStepper, check_guidance_rescale, guidance_table, host_drawer, make_ddim_sampling_parameters,
+                   make_ddim_timesteps)
 
 LOWER_ORDER_FINAL_BELOW = 15   # runs shorter than this take their last step at first order
 
@@ -69,6 +70,9 @@ class DPMSolverSampler(object):
         self.use_graph = os.environ.get("ALDM_NO_GRAPH", "0") != "1"
         # (global_batch, row_offset) when this process samples one shard of a larger batch (dist.py)
         self.noise_shard = getattr(model, "noise_shard", None)
+        # phi of Lin et al. 2023 (section 3.4), 0: off.  Sampler state, as in PLMSSampler, whose parameter lists this class
+        # carries: `sample` sets it on every call from its `guidance_rescale=` keyword (absent: 0), `dpm_sampling` reads it.
+        self.guidance_rescale = 0.0
 
     def register_buffer(self, name, attr):
         setattr(self, name, attr)
@@ -101,7 +105,9 @@ class DPMSolverSampler(object):
                img_callback=None, quantize_x0=False, eta=0.0, mask=None, x0=None, temperature=1.0,
                noise_dropout=0.0, score_corrector=None, corrector_kwargs=None, verbose=True, x_T=None,
                log_every_t=100, unconditional_guidance_scale=1.0, unconditional_conditioning=None, **kwargs):
-        """PLMSSampler.sample's parameter list; S is the grid parameter of make_ddim_timesteps."""
+        """PLMSSampler.sample's parameter list; S is the grid parameter of make_ddim_timesteps.  `guidance_rescale` is read from
+        **kwargs, as there, and becomes `self.guidance_rescale` for this run."""
+        self.guidance_rescale = check_guidance_rescale(kwargs.pop("guidance_rescale", 0.0))
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
         C, H, W = shape
         size = (batch_size, C, H, W)
@@ -136,7 +142,8 @@ class DPMSolverSampler(object):
                      quantize_denoised=False, mask=None, x0=None, img_callback=None, log_every_t=100, temperature=1.0,
                      noise_dropout=0.0, score_corrector=None, corrector_kwargs=None, unconditional_guidance_scale=1.0,
                      unconditional_conditioning=None):
-        """PLMSSampler.plms_sampling's parameter list and loop structure."""
+        """PLMSSampler.plms_sampling's parameter list and loop structure; guidance rescale: `self.guidance_rescale`."""
+        guidance_rescale = check_guidance_rescale(self.guidance_rescale)
         self._refuse(ddim_use_original_steps, quantize_denoised, score_corrector, noise_dropout)
         dev = torch.device("cuda")
         shape = tuple(shape)
@@ -158,11 +165,10 @@ class DPMSolverSampler(object):
             return img, intermediates
 
         # device tables in loop order; a sub-range has its own table (its own first and last step)
-        coef = torch.zeros(total_steps, 8)
-        coef[:, :5] = self.dpm_coef if total_steps == self.dpm_coef.shape[0] else self._table(total_steps)
-        coef[:, 5] = float(unconditional_guidance_scale)
-        coef[:, 6] = 1.0 if use_cfg else 0.0
-        coef = coef.to(dev)
+        # guidance rescale: the combine and the per-sample rescale run in a launch of their own in front of the step kernel
+        rescale = use_cfg and guidance_rescale > 0.0
+        coef = guidance_table(self.dpm_coef if total_steps == self.dpm_coef.shape[0] else self._table(total_steps),
+                              unconditional_guidance_scale, use_cfg, guidance_rescale).to(dev)
         nrep = 2 if use_cfg else 1
         t_tab = torch.from_numpy(time_range).float()[:, None].repeat(1, nrep * b).to(dev).contiguous()
         if mask is not None:
@@ -179,9 +185,12 @@ class DPMSolverSampler(object):
         x_cur, pred_x0 = img.clone(), torch.empty_like(img)
         step_idx = torch.zeros(1, device=dev, dtype=torch.int32)
         t_cur = t_tab[0].clone()
+        eps_g = torch.empty_like(img) if rescale else None   # the rescaled combined model output
 
         def step():
             eps = self._model_output(x_cur, t_cur, b, cond, unconditional_conditioning, use_cfg, prepared)
+            if rescale:
+                eps = ops.cfg_rescale_indexed(eps, eps_g, coef, step_idx)
             ops.dpmpp_step_indexed(x_cur, eps, pred_x0, coef, step_idx)
             ops.step_advance(step_idx, t_tab, t_cur)
         run_step = GraphStepper(step, self.use_graph)   # every step: eager once, captured at the next, replayed after

@@ -1482,6 +1482,28 @@ def dpmpp_step_indexed(x: torch.Tensor, eps: torch.Tensor, x0_buf: torch.Tensor,
     return x
 
 
+def cfg_rescale_indexed(eps: torch.Tensor, out: torch.Tensor, coef: torch.Tensor,
+                        step_idx: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The guidance combine with guidance rescale (aldm_cfg_rescale_indexed; Lin et al. 2023, section 3.4): per sample b of
+    eps [2, B, ...] = [uncond ; cond], e_g = e_u + s (e_c - e_u) and out[b] = (phi std(e_c) / std(e_g) + 1 - phi) e_g, the standard
+    deviations over the sample (the factor is 1 where std(e_g) == 0).  s = column 5 and phi = column 7 of the coef [S, >= 8] row
+    the int32 device counter `step_idx` selects (None: row 0).  out [B, ...] must not overlap eps; a step kernel then takes it as
+    its model output with the row's column 6 = 0."""
+    for t, n in ((eps, "eps"), (out, "out"), (coef, "coef")):
+        _chk(t, "cfg_rescale." + n)
+    if eps.dim() < 2 or eps.shape[0] != 2 or tuple(out.shape) != tuple(eps.shape[1:]) or out.numel() == 0:
+        raise RuntimeError(f"cfg_rescale: eps must be [2, B, ...] and out [B, ...], got {tuple(eps.shape)} and {tuple(out.shape)}")
+    if coef.dim() != 2:
+        raise RuntimeError(f"cfg_rescale.coef: expected a [S, >= 8] table, got {tuple(coef.shape)}")
+    if step_idx is not None and not (step_idx.dtype == torch.int32 and step_idx.is_cuda and step_idx.numel() == 1):
+        raise RuntimeError(f"cfg_rescale.step_idx: expected one int32 CUDA element, got {step_idx.dtype} {step_idx.device} "
+                           f"numel={step_idx.numel()}")
+    B = eps.shape[1]
+    _l.check(_l.load().aldm_cfg_rescale_indexed(eps.data_ptr(), out.data_ptr(), coef.data_ptr(), _p(step_idx), B,
+                                                out.numel() // B, coef.shape[1], _stream()), "cfg_rescale_indexed")
+    return out
+
+
 def step_advance(step_idx: torch.Tensor, t_tab: torch.Tensor, t_cur: torch.Tensor) -> None:
     """step_idx += 1; t_cur = t_tab[min(step_idx, S - 1)] on the device (aldm_step_advance)."""
     _chk(t_tab, "step_advance.t_tab"); _chk(t_cur, "step_advance.t_cur")

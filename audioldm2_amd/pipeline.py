@@ -289,6 +289,52 @@ def resolve_sampler(sampler, use_plms=False):
     return sampler
 
 
+def negative_batch(batch, negative_prompt):
+    """The batch whose conditioning is the unconditional half of classifier-free guidance under `negative_prompt` (a string, or
+    a list of one string per prompt): `batch` with `text` replaced and an empty transcription (`phoneme_idx` = the end mark
+    alone); every other entry is shared with `batch`."""
+    from .phoneme import phoneme_ids
+    B0 = len(batch["text"])
+    if isinstance(negative_prompt, str):
+        neg = [negative_prompt] * B0
+    else:
+        neg = list(negative_prompt)
+        if len(neg) != B0 or not all(isinstance(t, str) for t in neg):
+            raise ValueError(f"negative_prompt must be a string or a list of {B0} strings (one per prompt)")
+    out = dict(batch)
+    out["text"] = neg
+    out["phoneme_idx"] = phoneme_ids("", B0)
+    return out
+
+
+def _guidance_kwargs(kwargs, unconditional_guidance_scale, batch, ddim_steps):
+    """`negative_prompt` and `guidance_rescale` of generate_batch / generate_batch_masked (they travel in **kwargs like `sampler`):
+    -> (the negative batch or None, phi), refused before anything is drawn or computed."""
+    from .ddim import check_guidance_rescale
+    phi = check_guidance_rescale(kwargs.get("guidance_rescale", 0.0))
+    if phi != 0.0 and ddim_steps is None:
+        raise ValueError("guidance_rescale needs ddim_steps: the ancestral sampler has no guidance")
+    negative_prompt = kwargs.get("negative_prompt", None)
+    if negative_prompt is None:
+        return None, phi
+    if unconditional_guidance_scale == 1.0:
+        raise ValueError("negative_prompt needs unconditional_guidance_scale != 1.0: at scale 1.0 there is no unconditional half "
+                         "and the prompt would be silently ignored")
+    return negative_batch(batch, negative_prompt), phi
+
+
+def _tile_cond(c, n_gen):
+    """ddpm.py:1509-1523: the conditioning of B0 prompts repeated for n_gen candidates each (candidate-major)."""
+    for k in c.keys():
+        if isinstance(c[k], list):
+            c[k] = [torch.cat([e] * n_gen, dim=0) for e in c[k]]
+        elif isinstance(c[k], dict):
+            c[k] = {kk: torch.cat([vv] * n_gen, dim=0) for kk, vv in c[k].items()}
+        else:
+            c[k] = torch.cat([c[k]] * n_gen, dim=0)
+    return c
+
+
 class LatentDiffusion(nn.Module):
     """Sampling-path subset of ddpm.py's DDPM/LatentDiffusion with identical public signatures.
     State-dict layout is the reference's: `model.diffusion_model.*`, `first_stage_model.*`,
@@ -526,6 +572,12 @@ class LatentDiffusion(nn.Module):
                    unconditional_conditioning=None, use_plms=False, mask=None, **kwargs):
         """ddpm.py:1418-1474; `sampler="dpmpp_2m"` (a keyword of **kwargs, no reference counterpart) runs DPMSolverSampler."""
         sampler_name = resolve_sampler(kwargs.pop("sampler", None), use_plms)
+        # `guidance_rescale` (phi of Lin et al. 2023, a keyword of **kwargs too) goes to whichever of the three samplers runs
+        from .ddim import check_guidance_rescale
+        if check_guidance_rescale(kwargs.get("guidance_rescale", 0.0)) == 0.0:
+            kwargs.pop("guidance_rescale", None)   # off: today's call, unchanged
+        elif not (use_plms or sampler_name is not None or ddim):
+            raise ValueError("guidance_rescale needs ddim_steps: the ancestral sampler has no guidance")
         if mask is not None:
             shape = (self.channels, mask.size()[-2], mask.size()[-1])
         else:
@@ -753,6 +805,7 @@ class LatentDiffusion(nn.Module):
         read its batch size; we replay the draw and skip the 345 GFLOP encode."""
         assert x_T is None
         sampler = resolve_sampler(kwargs.get("sampler", None), use_plms)   # travels in **kwargs like `shard`
+        neg_batch, guidance_rescale = _guidance_kwargs(kwargs, unconditional_guidance_scale, batch, ddim_steps)
         if use_plms:
             assert ddim_steps is not None
         self.check_latent_t(self.latent_t_size)
@@ -766,15 +819,12 @@ class LatentDiffusion(nn.Module):
         self._cfg_dropout_draw()                                                                     # (R1b) every call but the first
         c = self.get_learned_conditioning_dict(batch)
         batch_size = B0 * n_gen
-        for k in c.keys():
-            if isinstance(c[k], list):
-                c[k] = [torch.cat([e] * n_gen, dim=0) for e in c[k]]
-            elif isinstance(c[k], dict):
-                c[k] = {kk: torch.cat([vv] * n_gen, dim=0) for kk, vv in c[k].items()}
-            else:
-                c[k] = torch.cat([c[k]] * n_gen, dim=0)
+        c = _tile_cond(c, n_gen)
         text = list(batch["text"]) * n_gen
-        if unconditional_guidance_scale != 1.0:
+        if neg_batch is not None:
+            # the negative prompt's conditioning is the unconditional half: a second conditioner pass, after the positive one
+            unconditional_conditioning = _tile_cond(self.get_learned_conditioning_dict(neg_batch), n_gen)
+        elif unconditional_guidance_scale != 1.0:
             unconditional_conditioning = {}
             for key, meta in self.cond_stage_model_metadata.items():
                 unconditional_conditioning[key] = self.cond_stage_models[
@@ -808,7 +858,8 @@ class LatentDiffusion(nn.Module):
                                          ddim_steps=ddim_steps, eta=ddim_eta,
                                          unconditional_guidance_scale=unconditional_guidance_scale,
                                          unconditional_conditioning=unconditional_conditioning,
-                                         use_plms=use_plms, **({} if sampler is None else {"sampler": sampler}))
+                                         use_plms=use_plms, **({} if sampler is None else {"sampler": sampler}),
+                                         **({} if guidance_rescale == 0.0 else {"guidance_rescale": guidance_rescale}))
         finally:
             self.noise_shard = None
         mel = self.decode_first_stage_cl(samples)  # [B, T, F, 1]
@@ -840,6 +891,7 @@ class LatentDiffusion(nn.Module):
         unmasked latent region (DDIM blends q_sample(x0, t) back in every step), regenerate the rest."""
         assert x_T is None
         sampler = resolve_sampler(kwargs.get("sampler", None), use_plms)
+        neg_batch, guidance_rescale = _guidance_kwargs(kwargs, unconditional_guidance_scale, batch, ddim_steps)
         if use_plms:
             assert ddim_steps is not None
         self._check_candidates(n_gen, batch.get("text"))
@@ -857,15 +909,12 @@ class LatentDiffusion(nn.Module):
         mask[:, int(h * time_mask_ratio_start_and_end[0]):int(h * time_mask_ratio_start_and_end[1]), :] = 0
         mask[:, :, int(w * freq_mask_ratio_start_and_end[0]):int(w * freq_mask_ratio_start_and_end[1])] = 0
         mask = mask[:, None, ...]
-        for k in c.keys():
-            if isinstance(c[k], list):
-                c[k] = [torch.cat([e] * n_gen, dim=0) for e in c[k]]
-            elif isinstance(c[k], dict):
-                c[k] = {kk: torch.cat([vv] * n_gen, dim=0) for kk, vv in c[k].items()}
-            else:
-                c[k] = torch.cat([c[k]] * n_gen, dim=0)
+        c = _tile_cond(c, n_gen)
         text = list(batch["text"]) * n_gen
-        if unconditional_guidance_scale != 1.0:
+        if neg_batch is not None:
+            # the negative prompt's conditioning is the unconditional half: a second conditioner pass, after the positive one
+            unconditional_conditioning = _tile_cond(self.get_learned_conditioning_dict(neg_batch), n_gen)
+        elif unconditional_guidance_scale != 1.0:
             unconditional_conditioning = {}
             for key, meta in self.cond_stage_model_metadata.items():
                 unconditional_conditioning[key] = self.cond_stage_models[
@@ -873,7 +922,8 @@ class LatentDiffusion(nn.Module):
         samples, _ = self.sample_log(cond=c, batch_size=batch_size, x_T=x_T, ddim=use_ddim, ddim_steps=ddim_steps,
                                      eta=ddim_eta, unconditional_guidance_scale=unconditional_guidance_scale,
                                      unconditional_conditioning=unconditional_conditioning, use_plms=use_plms,
-                                     mask=mask, x0=torch.cat([z] * n_gen), **({} if sampler is None else {"sampler": sampler}))
+                                     mask=mask, x0=torch.cat([z] * n_gen), **({} if sampler is None else {"sampler": sampler}),
+                                     **({} if guidance_rescale == 0.0 else {"guidance_rescale": guidance_rescale}))
         mel = self.decode_first_stage_cl(samples)
         waveform = self.mel_spectrogram_to_waveform(mel.view(mel.shape[0], mel.shape[1], mel.shape[2]),
                                                     savepath="", bs=None, name=batch.get("fname"), save=False)
@@ -996,23 +1046,31 @@ def wav_to_fbank(source, target_length=1024, fn_STFT=None):
     return _pad_spec(fbank, target_length), _pad_spec(log_mag, target_length), waveform
 
 
-def _sampler_kwargs(sampler):
+def _sampler_kwargs(sampler, negative_prompt=None, guidance_rescale=0.0):
     """What the two entry points add to generate_batch* for `sampler=`: nothing for None (today's call, unchanged); a named
-    sampler is deterministic, and these entry points have no eta parameter, so eta 0 goes with the name."""
-    return {} if resolve_sampler(sampler) is None else {"sampler": sampler, "ddim_eta": 0.0}
+    sampler is deterministic, and these entry points have no eta parameter, so eta 0 goes with the name.  `negative_prompt` and
+    `guidance_rescale` travel the same way, and only when set."""
+    kw = {} if resolve_sampler(sampler) is None else {"sampler": sampler, "ddim_eta": 0.0}
+    if negative_prompt is not None:
+        kw["negative_prompt"] = negative_prompt
+    if guidance_rescale != 0.0:
+        kw["guidance_rescale"] = guidance_rescale
+    return kw
 
 
 def super_resolution_and_inpainting(latent_diffusion, text, transcription="", original_audio_file_path=None,
                                     seed=42, ddim_steps=200, duration=None, batchsize=1, guidance_scale=2.5,
                                     n_candidate_gen_per_text=3, time_mask_ratio_start_and_end=(0.40, 0.6),
                                     freq_mask_ratio_start_and_end=(1.0, 1.0), latent_t_per_second=25.6,
-                                    config=None, sampler=None):
-    """pipeline.py:213-267: same signature and defaults, plus a trailing `sampler` (None: the reference's DDIM at eta 1;
-    "dpmpp_2m": DPM-Solver++(2M), deterministic, so ddim_eta=0.0 travels with it).  `original_audio_file_path` may also be a 1-D
+                                    config=None, negative_prompt=None, guidance_rescale=0.0, sampler=None):
+    """pipeline.py:213-267: same signature and defaults, plus `negative_prompt` (a string or one per prompt: its conditioning
+    replaces the unconditional half of the guidance), `guidance_rescale` (phi of Lin et al. 2023) and a trailing `sampler` (None:
+    the reference's DDIM at eta 1; "dpmpp_2m": DPM-Solver++(2M), deterministic, so ddim_eta=0.0 travels with it).  Pass the three
+    by keyword: `sampler` stays the last parameter, the two others sit in front of it.  `original_audio_file_path` may also be a 1-D
     float waveform at 16 kHz.  STFT/mel (a17), VAE encode (a18), masked DDIM, decode and vocoder all run
     on the HIP path."""
     from .stft import TacotronSTFT
-    sampler_kw = _sampler_kwargs(sampler)
+    sampler_kw = _sampler_kwargs(sampler, negative_prompt, guidance_rescale)
     seed_everything(int(seed))
     if config is not None:
         raise NotImplementedError("YAML configs are host glue of the reference; pass config=None")
@@ -1111,11 +1169,13 @@ def build_model(ckpt_path=None, config=None, device=None, model_name="audioldm2-
 
 def text_to_audio(latent_diffusion, text, transcription="", seed=42, ddim_steps=200, duration=10,
                   batchsize=1, guidance_scale=3.5, n_candidate_gen_per_text=3, latent_t_per_second=25.6,
-                  config=None, sampler=None):
+                  config=None, negative_prompt=None, guidance_rescale=0.0, sampler=None):
     """pipeline.py:181-211: same signature, side effects (sets latent_t_size) and return value
-    (np.float32 [batchsize, 1, samples]), plus a trailing `sampler` (None: the reference's DDIM at eta 1; "dpmpp_2m":
-    DPM-Solver++(2M) over `ddim_steps`, deterministic, so ddim_eta=0.0 travels with it)."""
-    sampler_kw = _sampler_kwargs(sampler)
+    (np.float32 [batchsize, 1, samples]), plus `negative_prompt` (a string or one per prompt: its conditioning replaces the
+    unconditional half of the guidance), `guidance_rescale` (phi of Lin et al. 2023, in [0, 1]; 0: off) and a trailing `sampler`
+    (None: the reference's DDIM at eta 1; "dpmpp_2m": DPM-Solver++(2M) over `ddim_steps`, deterministic, so ddim_eta=0.0 travels
+    with it).  Pass the three by keyword: `sampler` stays the last parameter, the two others sit in front of it."""
+    sampler_kw = _sampler_kwargs(sampler, negative_prompt, guidance_rescale)
     seed_everything(int(seed))
     batch = make_batch_for_text_to_audio(text, transcription=transcription, batchsize=batchsize)
     latent_diffusion.latent_t_size = int(duration * latent_t_per_second)

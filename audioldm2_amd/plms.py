@@ -28,7 +28,8 @@ import numpy as np
 import torch
 
 from . import ops
-from .ddim import GraphStepper, host_drawer, make_ddim_sampling_parameters, make_ddim_timesteps
+from .ddim import (GraphStepper, check_guidance_rescale, guidance_table, host_drawer, make_ddim_sampling_parameters,
+                   make_ddim_timesteps)
 
 
 class PLMSSampler(object):
@@ -40,6 +41,10 @@ class PLMSSampler(object):
         self.use_graph = os.environ.get("ALDM_NO_GRAPH", "0") != "1"
         # (global_batch, row_offset) when this process samples one shard of a larger batch (dist.py)
         self.noise_shard = getattr(model, "noise_shard", None)
+        # phi of Lin et al. 2023 (section 3.4), 0: off.  Sampler state like the schedule, not a parameter: `plms_sampling` and
+        # `p_sample_plms` keep the reference class's signatures, which have no **kwargs to take it.  `sample` sets it on every
+        # call from its `guidance_rescale=` keyword (absent: 0); a caller of the two other methods sets the attribute.
+        self.guidance_rescale = 0.0
 
     def register_buffer(self, name, attr):
         setattr(self, name, attr)
@@ -75,7 +80,9 @@ class PLMSSampler(object):
                img_callback=None, quantize_x0=False, eta=0.0, mask=None, x0=None, temperature=1.0,
                noise_dropout=0.0, score_corrector=None, corrector_kwargs=None, verbose=True, x_T=None,
                log_every_t=100, unconditional_guidance_scale=1.0, unconditional_conditioning=None, **kwargs):
-        """plms.py:91-154"""
+        """plms.py:91-154; `guidance_rescale` (phi of Lin et al. 2023; 0 or absent: off — the reference's step) is read from
+        **kwargs, so the signature stays the reference's, and becomes `self.guidance_rescale` for this run"""
+        self.guidance_rescale = check_guidance_rescale(kwargs.pop("guidance_rescale", 0.0))
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
         C, H, W = shape
         size = (batch_size, C, H, W)
@@ -113,7 +120,8 @@ class PLMSSampler(object):
                       quantize_denoised=False, mask=None, x0=None, img_callback=None, log_every_t=100, temperature=1.0,
                       noise_dropout=0.0, score_corrector=None, corrector_kwargs=None, unconditional_guidance_scale=1.0,
                       unconditional_conditioning=None):
-        """plms.py:156-258"""
+        """plms.py:156-258; guidance rescale: `self.guidance_rescale`"""
+        guidance_rescale = check_guidance_rescale(self.guidance_rescale)
         self._refuse(ddim_use_original_steps, quantize_denoised, score_corrector, noise_dropout)
         dev = torch.device("cuda")
         shape = tuple(shape)
@@ -136,11 +144,10 @@ class PLMSSampler(object):
 
         # device tables in loop order (i = 0 is the noisiest step, index = total_steps - 1)
         order = [total_steps - i - 1 for i in range(total_steps)]
-        coef = torch.zeros(total_steps, 8)
-        coef[:, :5] = self.plms_coef[order]
-        coef[:, 5] = float(unconditional_guidance_scale)
-        coef[:, 6] = 1.0 if use_cfg else 0.0
-        coef = coef.to(dev)
+        # guidance rescale: the combine and the per-sample rescale run in a launch of their own in front of the step kernels,
+        # so the history ring holds the rescaled e_t
+        rescale = use_cfg and guidance_rescale > 0.0
+        coef = guidance_table(self.plms_coef[order], unconditional_guidance_scale, use_cfg, guidance_rescale).to(dev)
         nrep = 2 if use_cfg else 1
         t_tab = torch.from_numpy(time_range).float()[:, None].repeat(1, nrep * b).to(dev).contiguous()
         if mask is not None:
@@ -158,9 +165,18 @@ class PLMSSampler(object):
         hist = torch.zeros((3,) + shape, device=dev, dtype=torch.float32)   # model outputs of the last three steps, slot = step % 3
         step_idx = torch.zeros(1, device=dev, dtype=torch.int32)
         t_cur = t_tab[0].clone()
+        eps_g = torch.empty_like(img) if rescale else None   # the rescaled combined model output of the replayed step
+
+        def model_output(x, t_row, out=None, idx=None):
+            """eps [2, b, ...] for the step kernel to combine, or with rescale the combined and rescaled [b, ...] (row: the
+            counter's, or row 0 — the step's row in the eager calls of step 0)"""
+            eps = self._model_output(x, t_row, b, cond, unconditional_conditioning, use_cfg, prepared)
+            if not rescale:
+                return eps
+            return ops.cfg_rescale_indexed(eps, torch.empty_like(img) if out is None else out, coef, idx)
 
         def step():
-            eps = self._model_output(x_cur, t_cur, b, cond, unconditional_conditioning, use_cfg, prepared)
+            eps = model_output(x_cur, t_cur, eps_g, step_idx)
             ops.plms_step_indexed(x_cur, eps, hist, coef, step_idx, pred_x0)
             ops.step_advance(step_idx, t_tab, t_cur)
         run_step = GraphStepper(step, self.use_graph)   # steps >= 1: eager once, captured at the next, replayed after
@@ -171,11 +187,11 @@ class PLMSSampler(object):
                 ops.inpaint_blend(x_cur, x0_d, draw().to(dev), mask_d, blend_coef[i])
             if i == 0:
                 # pseudo improved Euler (plms.py:341-345): provisional x_prev from e_t, a second pass at (x_prev, t_next)
-                e_t = self._model_output(x_cur, t_cur, b, cond, unconditional_conditioning, use_cfg, prepared)
+                e_t = model_output(x_cur, t_cur)
                 x_tmp, _ = ops.plms_first_step(x_cur, e_t, None, coef[0])
                 draw()                                                   # the noise_like of the provisional update
                 t_next = t_tab[min(1, total_steps - 1)]
-                e_next = self._model_output(x_tmp, t_next, b, cond, unconditional_conditioning, use_cfg, prepared)
+                e_next = model_output(x_tmp, t_next)
                 ops.plms_first_step(x_cur, e_t, e_next, coef[0], x_out=x_cur, pred_x0=pred_x0, hist=hist)
                 ops.step_advance(step_idx, t_tab, t_cur)
                 del e_t, e_next, x_tmp
@@ -205,21 +221,21 @@ class PLMSSampler(object):
         Python list `old_eps` (oldest first, at most the last three are read).  The same kernels as plms_sampling; the noise
         draws come from the host generator like `noise_like` on a CPU reference run, and are discarded (sigma = 0)."""
         self._refuse(use_original_steps, quantize_denoised, score_corrector, noise_dropout)
+        guidance_rescale = check_guidance_rescale(self.guidance_rescale)
         b = x.shape[0]
         use_cfg = not (unconditional_conditioning is None or unconditional_guidance_scale == 1.0)
+        rescale = use_cfg and guidance_rescale > 0.0
         x = x.float().contiguous()
-        coef = torch.zeros(4, 8)
-        coef[:, :5] = self.plms_coef[index]
-        coef[:, 5] = float(unconditional_guidance_scale)
-        coef[:, 6] = 1.0 if use_cfg else 0.0
-        coef = coef.to(x.device)
+        coef = guidance_table(self.plms_coef[index].reshape(1, 5).repeat(4, 1), unconditional_guidance_scale, use_cfg,
+                              guidance_rescale).to(x.device)
         nrep = 2 if use_cfg else 1
 
         def noise_like():
             torch.randn((1, *x.shape[1:])) if repeat_noise else torch.randn(x.shape)
 
         def model_output(xx, tt):
-            return self._model_output(xx, tt.float().repeat(nrep), b, c, unconditional_conditioning, use_cfg, None)
+            eps = self._model_output(xx, tt.float().repeat(nrep), b, c, unconditional_conditioning, use_cfg, None)
+            return ops.cfg_rescale_indexed(eps, torch.empty_like(x), coef) if rescale else eps
         e_t = model_output(x, t)
         hist = torch.zeros((3,) + tuple(x.shape), device=x.device, dtype=torch.float32)
         old_eps = list(old_eps or [])[-3:]

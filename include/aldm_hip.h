@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 /* ---- library / error ------------------------------------------------------------------ */
-int aldm_version(void);              /* ABI version (13), bumped on any struct / entry change */
+int aldm_version(void);              /* ABI version (14), bumped on any struct / entry change */
 const char* aldm_last_error(void);   /* message of the last failing call on this thread     */
 
 /* ---- activations usable as prologue (applied to the gathered input) or epilogue -------- */
@@ -494,6 +494,16 @@ int aldm_plms_step_indexed(float* x, const float* eps, float* hist, const float*
  * The counter is not range-checked, as in aldm_ddim_step_indexed: aldm_step_advance saturates it at the last row.           */
 int aldm_dpmpp_step_indexed(float* x, const float* eps, float* x0_buf, const float* coef_tab, const int* step_idx, int64_t n,
                             int coef_ld, void* stream);
+/* Classifier-free guidance combine with guidance rescale (Lin et al. 2023, "Common Diffusion Noise Schedules and Sample Steps are
+ * Flawed", section 3.4; ABI v14).  s = step_idx ? *step_idx : 0, coef = coef_tab[s] (rows of coef_ld >= 8 floats): coef[5] the
+ * guidance scale g, coef[7] = phi.  eps holds [e_uncond ; e_cond] as [2, B, n_s]; per sample b over its n_s elements:
+ *   e_g = e_u + g*(e_c - e_u); f = phi * std(e_c) / std(e_g) + (1 - phi); out[b] = f * e_g.
+ * f = 1 when std(e_g) == 0 or n_s == 1 (the textbook form gives NaN there).  Two-pass statistics in fp32 in a fixed order: results
+ * are bitwise reproducible.  One launch, one workgroup per sample.  out [B, n_s] must not overlap eps; eps and coef_tab are not
+ * written; a non-finite input reaches every output of its sample and no other sample.  A step kernel then takes out as its
+ * [1, n] model output (coef[6] == 0).                                                                                            */
+int aldm_cfg_rescale_indexed(const float* eps, float* out, const float* coef_tab, const int* step_idx, int B, int64_t n_s,
+                             int coef_ld, void* stream);
 /* *step_idx += 1 and t_cur[0..nt) = t_tab[min(*step_idx, steps-1)] (the next step's timestep row, the UNet's static input;
  * the time_range of ddim.py:205-213 stored as floats, one row per step in loop order)                                  */
 int aldm_step_advance(int* step_idx, const float* t_tab, float* t_cur, int nt, int steps, void* stream);
