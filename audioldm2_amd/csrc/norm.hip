@@ -14,12 +14,15 @@ namespace aldm {
 //         group adds the group's thread partials in a fixed order -> ws[b][chunk][g] = {sum, sumsq}.
 // Pass 2: grid (B).  double-precision combine of the chunk partials, mean/rstd, then
 //         scale[b,c] = rstd*gamma[c], shift[b,c] = beta[c] - mean*rstd*gamma[c].
+// Small samples take a one-launch FUSED form instead (below), optionally with the operand split in the same launch.  Which form a
+// shape takes is decided in groupnorm_plan() alone; aldm_groupnorm_plan reports it (form, group slices, groups per block, chunks,
+// column passes, threads that hold data) so that a test can assert the form it reached.
 constexpr int GN_ITERS = 16;
 constexpr int GN_UNROLL = 8;  // pixel loads in flight per thread
 
 // Numerics: E[x^2] - E[x]^2 over raw fp32 sums loses the variance as soon as |mean| >> std (a trained checkpoint's
 // post-conv activations; ATen's GroupNorm is Welford).  Here every thread accumulates sum / sum of squares of
-// (x - pivot) with pivot = the first value it sees (same group, so x - pivot is of the order of the group's spread),
+// (x - pivot) with pivot = the median of the first three values it sees (same group, so x - pivot is of the order of the group's spread),
 // turns them into (n, mean, M2 = sum (x - mean)^2) and partials are merged with Chan's parallel-variance formula in
 // fp64, in a fixed order (deterministic, no atomics): M2 = sum M2_t + sum n_t (mean_t - mean)^2.
 struct GnPart {
@@ -80,7 +83,11 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const float* __restrict
 #pragma unroll
             for (int u = 0; u < GN_UNROLL; ++u) sa[u] = sq[u] = 0.f;
             int p = p0 + ty;
-            const float pivot = src[(int64_t)p * pitch];
+            // pivot: the median of three of the first pixel's four values.  ONE of them (round 13: a single outlier sqrt(n) spreads
+            // high sitting first in a thread's walk) must not become the pivot — every other value of the thread would sit at
+            // -outlier and ss - s * md below cancel: rstd 1e-5 off for a group one thread wide.  Any of the values serves otherwise.
+            const f32x4 pv = *reinterpret_cast<const f32x4*>(src + (int64_t)p * pitch);
+            const float pivot = fmaxf(fminf(pv[0], pv[1]), fminf(fmaxf(pv[0], pv[1]), pv[2]));
             int cnt = 0;
             for (; p + (GN_UNROLL - 1) * rows < p1; p += GN_UNROLL * rows) {
                 f32x4 v[GN_UNROLL];
@@ -440,6 +447,57 @@ static void gn_geometry(int P, int C, int* cols, int* rows, int* chunk_px, int* 
     *chunks = (P + *chunk_px - 1) / *chunk_px;
 }
 
+// The ONE place that decides which launch form a GroupNorm takes (aldm_groupnorm_plan reports it; groupnorm_launch follows it).
+struct GnPlan {
+    int form;             // ALDM_GN_CHUNKED | ALDM_GN_FUSED | ALDM_GN_FUSED_SPLIT
+    int gs, gpb;          // the rule's group slices per sample and groups per block, gs * gpb = G (the fused grid is (gs, B); gpb > 4
+                          // is what sends a sample that is small enough to the chunked form, whose blocks each see all G groups)
+    int chunks, chunk_px; // grid.x and pixels per block of the chunked form; 1 and P in the fused forms
+    int cols, rows;       // float4 columns per pass and pixel rows of the 256-thread block
+    int passes;           // column passes per block
+    int active;           // threads of a block's first pass that hold data: cols * min(rows, pixels of the block)
+};
+
+static GnPlan groupnorm_plan(int B, int P, int C, int C1, int G, bool want_split) {
+    GnPlan pl;
+    static const int64_t fused_max = [] {   // A/B override: largest sample (elements) handled by the one-launch form
+        const char* e = getenv("ALDM_GN_FUSED_MAX");
+        return e ? (int64_t)atoll(e) : (int64_t)1 << 17;
+    }();
+    // (2^17 elements per sample since round 6: round 2 chose 2^20 on isolated launches; INSIDE the replayed bf16x6 step the level-1
+    //  slabs — 1024 pixels x 256-640 channels — are 0.05-0.12 ms per step faster on the chunked statistics + finalize + split_rows form,
+    //  f16x3 indifferent: profiles/r06_step_ab_gn_fused_max.txt)
+    // group slices per sample: enough blocks to cover the chip (>= 256 / B), each owning gpb = G / gs whole groups
+    int gs = 1;
+    while (gs < G && gs * B < 256 && G % (gs * 2) == 0) gs *= 2;
+    pl.gs = gs;
+    pl.gpb = G / gs;
+    // one launch, blocks own whole groups: up to 1024 pixels per sample (measured, tools/gn_bench.py / profiles/r02_gn_bench.txt:
+    // 6.6-8.5 us against 7.9-12.4 for the chunked two-launch form; at 4096 pixels a block's narrow channel slab reads 32 bytes
+    // per 512-byte row and loses, 24.6 vs 12.0 us)
+    if ((int64_t)P * C <= fused_max && P <= 1024 && pl.gpb <= 4) {
+        const int c4b = pl.gpb * (C / G) / 4;
+        const int slab = pl.gpb * (C / G);
+        static const bool fuse_split = [] {   // A/B override: ALDM_GN_SPLIT_FUSED=0 keeps statistics and split in two launches
+            const char* e = getenv("ALDM_GN_SPLIT_FUSED");
+            return e == nullptr || e[0] != '0';
+        }();
+        pl.form = want_split && fuse_split && slab % 8 == 0 && slab <= 256 && C1 % 8 == 0 ? ALDM_GN_FUSED_SPLIT : ALDM_GN_FUSED;
+        pl.cols = c4b < 256 ? c4b : 256;
+        pl.rows = 256 / pl.cols;
+        pl.chunk_px = P;
+        pl.chunks = 1;
+        pl.passes = (c4b + pl.cols - 1) / pl.cols;
+    } else {
+        pl.form = ALDM_GN_CHUNKED;
+        gn_geometry(P, C, &pl.cols, &pl.rows, &pl.chunk_px, &pl.chunks);
+        pl.passes = (C / 4 + pl.cols - 1) / pl.cols;
+    }
+    const int px = P < pl.chunk_px ? P : pl.chunk_px;
+    pl.active = pl.cols * (pl.rows < px ? pl.rows : px);
+    return pl;
+}
+
 }  // namespace aldm
 
 using namespace aldm;
@@ -456,6 +514,30 @@ extern "C" int aldm_split_rows_f16(const float* x1, const float* x2, int C1, int
                                    const float* shift, int act, float slope, void* dst, void* dst_raw, int raw_parts, float f16_scale,
                                    void* stream);
 
+// Host-only query (ABI v15): the launch form aldm_groupnorm_stats (want_split = 0) / aldm_groupnorm_split{,_f16} (want_split = 1)
+// take for this shape, from the same function the launcher follows.  Out pointers may be null.
+extern "C" int aldm_groupnorm_plan(int B, int P, int C1, int C2, int G, int want_split, int* form, int* group_slices,
+                                   int* groups_per_block, int* chunks, int* chunk_px, int* cols, int* rows, int* passes,
+                                   int* active_threads) {
+    const int C = C1 + C2;
+    ALDM_CHECK(B > 0 && P > 0 && C1 > 0 && C2 >= 0, "aldm_groupnorm_plan: bad shape (B=%d P=%d C1=%d C2=%d)", B, P, C1, C2);
+    ALDM_CHECK(G > 0 && G <= 64 && C % G == 0 && (C / G) % 4 == 0 && C1 % 4 == 0,
+               "aldm_groupnorm_plan: need C%%G==0, (C/G)%%4==0, C1%%4==0 (C1=%d C2=%d G=%d)", C1, C2, G);
+    ALDM_CHECK(!want_split || (C % 32 == 0 && C1 % 8 == 0 && C2 % 8 == 0),
+               "aldm_groupnorm_plan: a split image needs (C1+C2) %% 32 == 0, C1 %% 8 == 0 (C1=%d C2=%d)", C1, C2);
+    const GnPlan pl = groupnorm_plan(B, P, C, C1, G, want_split != 0);
+    if (form) *form = pl.form;
+    if (group_slices) *group_slices = pl.gs;
+    if (groups_per_block) *groups_per_block = pl.gpb;
+    if (chunks) *chunks = pl.chunks;
+    if (chunk_px) *chunk_px = pl.chunk_px;
+    if (cols) *cols = pl.cols;
+    if (rows) *rows = pl.rows;
+    if (passes) *passes = pl.passes;
+    if (active_threads) *active_threads = pl.active;
+    return 0;
+}
+
 static int groupnorm_launch(const float* x1, const float* x2, int B, int P, int C1, int C2, int G, float eps,
                             const float* gamma, const float* beta, float* scale, float* shift, float* ws, void* dst,
                             void* dst_raw, int parts, int act, void* stream, int raw_parts = 0, float f16_scale = 0.f) {
@@ -466,45 +548,23 @@ static int groupnorm_launch(const float* x1, const float* x2, int B, int P, int 
     ws = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(ws) + 7) & ~uintptr_t(7));   // fp64 partials
     ALDM_CHECK(G > 0 && G <= 64 && C % G == 0 && (C / G) % 4 == 0 && C1 % 4 == 0,
                "aldm_groupnorm_stats: need C%%G==0, (C/G)%%4==0, C1%%4==0 (C1=%d C2=%d G=%d)", C1, C2, G);
-    int cols, rows, chunk_px, chunks;
-    gn_geometry(P, C, &cols, &rows, &chunk_px, &chunks);
+    const GnPlan pl = groupnorm_plan(B, P, C, C1, G, dst != nullptr);
     hipStream_t st = (hipStream_t)stream;
-    static const int64_t fused_max = [] {   // A/B override: largest sample (elements) handled by the one-launch form
-        const char* e = getenv("ALDM_GN_FUSED_MAX");
-        return e ? (int64_t)atoll(e) : (int64_t)1 << 17;
-    }();
-    // (2^17 elements per sample since round 6: round 2 chose 2^20 on isolated launches; INSIDE the replayed bf16x6 step the level-1
-    //  slabs — 1024 pixels x 256-640 channels — are 0.05-0.12 ms per step faster on the chunked statistics + finalize + split_rows form,
-    //  f16x3 indifferent: profiles/r06_step_ab_gn_fused_max.txt)
-    // group slices per sample: enough blocks to cover the chip (>= 256 / B), each owning gpb = G / gs whole groups
-    int gs = 1;
-    while (gs < G && gs * B < 256 && G % (gs * 2) == 0) gs *= 2;
-    const int gpb = G / gs;
-    // one launch, blocks own whole groups: up to 1024 pixels per sample (measured, tools/gn_bench.py / profiles/r02_gn_bench.txt:
-    // 6.6-8.5 us against 7.9-12.4 for the chunked two-launch form; at 4096 pixels a block's narrow channel slab reads 32 bytes
-    // per 512-byte row and loses, 24.6 vs 12.0 us)
-    if ((int64_t)P * C <= fused_max && P <= 1024 && gpb <= 4) {
-        const int c4b = gpb * (C / G) / 4;
-        const int fcols = c4b < 256 ? c4b : 256, frows = 256 / fcols;
-        const int slab = gpb * (C / G);
-        static const bool fuse_split = [] {   // A/B override: ALDM_GN_SPLIT_FUSED=0 keeps statistics and split in two launches
-            const char* e = getenv("ALDM_GN_SPLIT_FUSED");
-            return e == nullptr || e[0] != '0';
-        }();
-        if (dst && fuse_split && slab % 8 == 0 && slab <= 256 && C1 % 8 == 0) {
-            // statistics + apply + activation + operand split in ONE launch (round 3)
-            hipLaunchKernelGGL(gn_partial_kernel<true>, dim3(gs, B), dim3(256), 0, st, x1, x2, P, C1, C2, G, fcols, frows, P, ws,
-                               eps, gamma, beta, scale, shift, gpb, reinterpret_cast<char*>(dst),
-                               reinterpret_cast<char*>(dst_raw), parts, act, raw_parts, f16_scale);
-            ALDM_LAUNCH_CHECK("aldm_groupnorm_split");
-            return 0;
-        }
-        hipLaunchKernelGGL(gn_partial_kernel<true>, dim3(gs, B), dim3(256), 0, st, x1, x2, P, C1, C2, G, fcols,
-                           frows, P, ws, eps, gamma, beta, scale, shift, gpb, nullptr, nullptr, 3, ALDM_ACT_NONE);
+    if (pl.form == ALDM_GN_FUSED_SPLIT) {
+        // statistics + apply + activation + operand split in ONE launch (round 3)
+        hipLaunchKernelGGL(gn_partial_kernel<true>, dim3(pl.gs, B), dim3(256), 0, st, x1, x2, P, C1, C2, G, pl.cols, pl.rows, P, ws,
+                           eps, gamma, beta, scale, shift, pl.gpb, reinterpret_cast<char*>(dst),
+                           reinterpret_cast<char*>(dst_raw), parts, act, raw_parts, f16_scale);
+        ALDM_LAUNCH_CHECK("aldm_groupnorm_split");
+        return 0;
+    }
+    if (pl.form == ALDM_GN_FUSED) {
+        hipLaunchKernelGGL(gn_partial_kernel<true>, dim3(pl.gs, B), dim3(256), 0, st, x1, x2, P, C1, C2, G, pl.cols,
+                           pl.rows, P, ws, eps, gamma, beta, scale, shift, pl.gpb, nullptr, nullptr, 3, ALDM_ACT_NONE);
     } else {
-        hipLaunchKernelGGL(gn_partial_kernel<false>, dim3(chunks, B), dim3(256), 0, st, x1, x2, P, C1, C2, G,
-                           cols, rows, chunk_px, ws, eps, gamma, beta, scale, shift, G);
-        hipLaunchKernelGGL(gn_finalize_kernel, dim3(B), dim3(256), 0, st, ws, chunks, P, C, G, eps, gamma,
+        hipLaunchKernelGGL(gn_partial_kernel<false>, dim3(pl.chunks, B), dim3(256), 0, st, x1, x2, P, C1, C2, G,
+                           pl.cols, pl.rows, pl.chunk_px, ws, eps, gamma, beta, scale, shift, G);
+        hipLaunchKernelGGL(gn_finalize_kernel, dim3(B), dim3(256), 0, st, ws, pl.chunks, P, C, G, eps, gamma,
                            beta, scale, shift);
     }
     ALDM_LAUNCH_CHECK("aldm_groupnorm_stats");

@@ -11,11 +11,12 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ALDM_LIB_PATH") or os.path.join(_HERE, "libaldm_hip.so")  # override: debug builds
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 ACT_NONE, ACT_SILU, ACT_LRELU, ACT_TANH, ACT_LOGCLAMP, ACT_GELU, ACT_GELU_TANH = range(7)
 B_PACKED, B_NT = 0, 1
 EPI_PLAIN, EPI_GEGLU, EPI_QKV = 0, 1, 2
+GN_CHUNKED, GN_FUSED, GN_FUSED_SPLIT = 0, 1, 2
 FMT_BF16, FMT_F16 = 0, 1
 
 
@@ -97,6 +98,7 @@ _SIGS = {
                                        C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p]),
     "aldm_gn_ws_floats": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "aldm_groupnorm_plan": (C.c_int, [C.c_int] * 6 + [C.POINTER(C.c_int)] * 9),
     "aldm_groupnorm_split": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                        C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_int, C.c_void_p]),

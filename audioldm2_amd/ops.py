@@ -992,6 +992,23 @@ def gn_stats(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, *, groups
     return ss[0], ss[1]
 
 
+GN_FORMS = ("chunked", "fused", "fused_split")   # lib.GN_CHUNKED, GN_FUSED, GN_FUSED_SPLIT
+
+
+def groupnorm_plan(B: int, P: int, C1: int, C2: int = 0, groups: int = 32, want_split: bool = False) -> dict:
+    """The launch form gn_stats (want_split=False) / gn_split (True) take for this shape (aldm_groupnorm_plan; host only):
+    {"form": "chunked" | "fused" | "fused_split", "group_slices", "groups_per_block", "chunks", "chunk_px", "cols", "rows",
+    "passes", "active_threads"} — see include/aldm_hip.h."""
+    import ctypes
+    out = [ctypes.c_int() for _ in range(9)]
+    _l.check(_l.load().aldm_groupnorm_plan(B, P, C1, C2, groups, 1 if want_split else 0, *[ctypes.byref(o) for o in out]),
+             "groupnorm_plan")
+    keys = ("form", "group_slices", "groups_per_block", "chunks", "chunk_px", "cols", "rows", "passes", "active_threads")
+    plan = {k: o.value for k, o in zip(keys, out)}
+    plan["form"] = GN_FORMS[plan["form"]]
+    return plan
+
+
 def gn_split(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, *, groups: int = 32, eps: float = 1e-5,
              x2: Optional[torch.Tensor] = None, act: int = ACT_NONE, want_raw: bool = False):
     """split(act(GroupNorm(x ++ x2))) as a SplitT — gn_stats + split_rows in one call (one launch up to 1024 pixels per

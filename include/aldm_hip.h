@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 /* ---- library / error ------------------------------------------------------------------ */
-int aldm_version(void);              /* ABI version (14), bumped on any struct / entry change */
+int aldm_version(void);              /* ABI version (15), bumped on any struct / entry change */
 const char* aldm_last_error(void);   /* message of the last failing call on this thread     */
 
 /* ---- activations usable as prologue (applied to the gathered input) or epilogue -------- */
@@ -304,6 +304,19 @@ int aldm_groupnorm_stats(const float* x1, const float* x2, int B, int P, int C1,
                          int G, float eps, const float* gamma, const float* beta,
                          float* scale, float* shift, float* ws, void* stream);
 int64_t aldm_gn_ws_floats(int B, int P, int C, int G);
+/* The launch form of a GroupNorm (ABI v15; host only, no launch), from the one function the launchers follow: want_split = 0 asks
+ * for aldm_groupnorm_stats, 1 for aldm_groupnorm_split{,_f16}.  form: ALDM_GN_CHUNKED = partial statistics per (pixel chunk,
+ * sample) + a finalize launch (+ aldm_split_rows for a split); ALDM_GN_FUSED = one launch whose blocks own whole groups (+
+ * aldm_split_rows for a split); ALDM_GN_FUSED_SPLIT = statistics, apply, activation and operand split in that one launch.
+ * group_slices x groups_per_block = G is the rule's block ownership (the fused grid is (group_slices, B); more than 4 groups per
+ * block, B >= 64 with G = 32, sends even a small sample to the chunked form, whose blocks each see all G groups); chunks x chunk_px
+ * the chunked grid (1 x P when fused); cols x rows the 256-thread block as float4 columns x pixel rows; passes the column passes
+ * of a block; active_threads the threads of a block's first pass that hold data.  $ALDM_GN_FUSED_MAX and $ALDM_GN_SPLIT_FUSED
+ * (read once) act inside.  Out pointers may be NULL.  For tests, which reach a form by shape and assert here which one.        */
+enum { ALDM_GN_CHUNKED = 0, ALDM_GN_FUSED = 1, ALDM_GN_FUSED_SPLIT = 2 };
+int aldm_groupnorm_plan(int B, int P, int C1, int C2, int G, int want_split, int* form, int* group_slices,
+                        int* groups_per_block, int* chunks, int* chunk_px, int* cols, int* rows, int* passes,
+                        int* active_threads);
 /* GroupNorm + activation (ALDM_ACT_NONE | ALDM_ACT_SILU) + operand split in one call (ABI v6): dst = split(act(GroupNorm(x1 ++
  * x2))) as a split image with `parts` parts, dst_raw (optional) = split(x1 ++ x2) — the image aldm_groupnorm_stats followed by
  * aldm_split_rows writes, bit for bit.  Samples of up to 1024 pixels run as ONE launch (a block owns whole groups: it reads its

@@ -148,6 +148,46 @@ def test_attention_query_tiles_rule():
         assert ops.attention_query_tiles(B, heads, Lq) == tiles, (B, heads, Lq)
 
 
+def test_groupnorm_plan_rule():
+    """aldm_groupnorm_plan (host only): the one rule by which aldm_groupnorm_stats / aldm_groupnorm_split pick their launch form.
+    Group slices double while slices * B < 256 (groups per block 1 up to B = 15, 2 up to 31, 4 up to 63, 8 from 64 with G = 32);
+    fused while P * C <= 2^17, P <= 1024 and at most 4 groups per block; the split joins the fused launch when the block's channel
+    slab is a multiple of 8, at most 256, and C1 % 8 == 0.  ($ALDM_GN_FUSED_MAX / $ALDM_GN_SPLIT_FUSED, read once per process,
+    override the rule: this table is the rule's, with the variables unset.)"""
+    from audioldm2_amd import ops
+    for v in ("ALDM_GN_FUSED_MAX", "ALDM_GN_SPLIT_FUSED"):
+        assert v not in os.environ, f"{v} overrides the GroupNorm rule: unset it to test the rule"
+    # (B, P, C1, C2, G, want_split) -> (form, group slices, groups per block, chunks, chunk_px, cols, rows, passes, active threads)
+    table = (
+        ((2, 64, 128, 0, 32, False), ("fused", 32, 1, 1, 64, 1, 256, 1, 64)),
+        ((15, 64, 128, 0, 32, True), ("fused", 32, 1, 1, 64, 1, 256, 1, 64)),             # slab of 4 channels: no 16-byte pieces
+        ((16, 64, 128, 0, 32, True), ("fused_split", 16, 2, 1, 64, 2, 128, 1, 128)),
+        ((31, 64, 128, 0, 32, False), ("fused", 16, 2, 1, 64, 2, 128, 1, 128)),
+        ((32, 64, 128, 0, 32, False), ("fused", 8, 4, 1, 64, 4, 64, 1, 256)),
+        ((63, 64, 128, 0, 32, False), ("fused", 8, 4, 1, 64, 4, 64, 1, 256)),
+        ((64, 64, 128, 0, 32, False), ("chunked", 4, 8, 1, 128, 32, 8, 1, 256)),
+        ((2, 1024, 128, 0, 32, False), ("fused", 32, 1, 1, 1024, 1, 256, 1, 256)),        # P * C = 2^17 exactly
+        ((2, 1024, 256, 0, 32, False), ("chunked", 32, 1, 16, 64, 64, 4, 1, 256)),        # P * C above it
+        ((2, 1025, 64, 0, 16, False), ("chunked", 16, 1, 5, 256, 16, 16, 1, 256)),        # P above 1024
+        ((16, 256, 384, 384, 32, True), ("chunked", 16, 2, 16, 16, 192, 1, 1, 192)),
+        ((16, 48, 1280, 1280, 32, True), ("fused_split", 16, 2, 1, 48, 40, 6, 1, 240)),
+        ((32, 48, 1280, 1280, 32, True), ("fused", 8, 4, 1, 48, 80, 3, 1, 240)),          # slab of 320 channels > 256
+        ((16, 64, 388, 252, 32, False), ("fused", 16, 2, 1, 64, 10, 25, 1, 250)),
+        ((1, 130, 1280, 0, 32, False), ("chunked", 32, 1, 9, 16, 256, 1, 2, 256)),
+        ((2, 70, 2560, 0, 32, False), ("chunked", 32, 1, 5, 16, 256, 1, 3, 256)),
+        ((2, 40, 2048, 0, 1, False), ("fused", 1, 1, 1, 40, 256, 1, 2, 256)),
+        ((1, 300, 256, 0, 64, True), ("fused", 64, 1, 1, 300, 1, 256, 1, 256)),
+        ((64, 40, 256, 0, 64, False), ("chunked", 4, 16, 1, 64, 64, 4, 1, 256)),
+    )
+    keys = ("form", "group_slices", "groups_per_block", "chunks", "chunk_px", "cols", "rows", "passes", "active_threads")
+    for args, want in table:
+        assert tuple(ops.groupnorm_plan(*args)[k] for k in keys) == want, (args, ops.groupnorm_plan(*args))
+    for args, msg in (((2, 64, 100, 0, 32), "C%G==0"), ((2, 64, 128, 0, 65), "C%G==0"), ((2, 64, 130, 126, 32), "C1%4==0"),
+                      ((0, 64, 128, 0, 32), "bad shape"), ((2, 64, 132, 124, 32, True), "split image needs")):
+        with pytest.raises(RuntimeError, match=msg):
+            ops.groupnorm_plan(*args)
+
+
 def test_missing_library_fails_loudly(tmp_path, monkeypatch):
     from audioldm2_amd import lib
     monkeypatch.setattr(lib, "_lib", None)

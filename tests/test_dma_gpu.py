@@ -356,7 +356,8 @@ def test_dma_ws_falls_back_when_not_eligible(ops):
     (16, 1024, 256, 0, True),     # UNet level 1, 16 samples: two groups per block, one launch
     (16, 256, 384, 384, True),    # skip concat at level 2
     (16, 64, 640, 0, False),      # SpatialTransformer.norm at level 3 (no activation)
-    (16, 1024, 384, 128, True),   # concat with a group straddling ... the x1 / x2 seam stays piece aligned (C1 % 8 == 0)
+    (16, 1024, 384, 128, True),   # concat whose x1 / x2 seam lies BETWEEN groups (Cg = 16, 384 = 24 * 16) and stays piece aligned
+                                  # (C1 % 8 == 0); a seam inside a group: tests/test_norm_forms_gpu.py (384 + 256, Cg = 20)
     (2, 1024, 128, 0, True),      # batch 2: one group per block, slab of 4 channels -> the two-launch form
     (3, 4096, 128, 128, True),    # level 0: too many pixels for the one-launch form
 ])
