@@ -604,6 +604,57 @@ __global__ void inpaint_blend_kernel(const float* __restrict__ x0, const float* 
     }
 }
 
+// VAE posterior sample fused with the forward diffusion to the sampler's first noise level (audio-to-audio, SDEdit):
+//   lv = clamp(logvar, -30, 20); std = exp(0.5 lv); z = scale*(mean + std*n_post); x_t[r] = sa*z[r % B0] + so*n_enc[r]
+// coef = {scale, sa = sqrt(abar), so = sqrt(1 - abar)}.  One thread per (source sample, pixel): adjacent threads take adjacent
+// pixels, each reads its 2C contiguous channels-last moments as 16-byte words and writes C channel planes (NCHW), every plane
+// store coalesced across the wave.  The clamp is two selects, so a NaN logvar stays NaN as under torch.clamp (fminf / fmaxf
+// would return the bound).
+__global__ void posterior_qsample_kernel(const float* __restrict__ moments_cl, const float* __restrict__ n_post,
+                                         const float* __restrict__ n_enc, const float* __restrict__ coef,
+                                         float* __restrict__ z, float* __restrict__ x_t, int B0, int n_gen, int C, int64_t hw) {
+    const float scale = coef[0], sa = coef[1], so = coef[2];
+    const int C4 = C >> 2;
+    const int64_t total = (int64_t)B0 * hw;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t b = i / hw, p = i - b * hw;
+        const float* m = moments_cl + i * 2 * C;
+        for (int c4 = 0; c4 < C4; ++c4) {
+            const f32x4 mean = *reinterpret_cast<const f32x4*>(m + 4 * c4);
+            const f32x4 logvar = *reinterpret_cast<const f32x4*>(m + C + 4 * c4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float lv = logvar[e];
+                lv = lv < -30.0f ? -30.0f : lv;
+                lv = lv > 20.0f ? 20.0f : lv;
+                const float sd = expf(0.5f * lv);
+                const int64_t plane = (int64_t)(4 * c4 + e) * hw + p;
+                const int64_t j = b * C * hw + plane;
+                const float zv = scale * (mean[e] + sd * n_post[j]);
+                z[j] = zv;
+                const float az = sa * zv;
+                for (int g = 0; g < n_gen; ++g) {
+                    const int64_t k = ((int64_t)g * B0 + b) * C * hw + plane;   // candidate-major: row r = g*B0 + b reads z[r % B0]
+                    x_t[k] = az + so * n_enc[k];
+                }
+            }
+        }
+    }
+}
+
+extern "C" int aldm_posterior_qsample(const float* moments_cl, const float* n_post, const float* n_enc, const float* coef, float* z,
+                                      float* x_t, int B0, int n_gen, int C, int64_t hw, void* stream) {
+    ALDM_CHECK(moments_cl && n_post && n_enc && coef && z && x_t, "aldm_posterior_qsample: null pointer");
+    ALDM_CHECK(B0 > 0 && n_gen > 0 && hw > 0, "aldm_posterior_qsample: B0=%d, n_gen=%d and hw=%lld must be positive", B0, n_gen,
+               (long long)hw);
+    ALDM_CHECK(C > 0 && C % 4 == 0, "aldm_posterior_qsample: C=%d must be a positive multiple of 4", C);
+    ALDM_CHECK(((uintptr_t)moments_cl & 15) == 0, "aldm_posterior_qsample: moments_cl must be 16-byte aligned");
+    hipLaunchKernelGGL(posterior_qsample_kernel, dim3(ew_blocks((int64_t)B0 * hw)), dim3(256), 0, (hipStream_t)stream, moments_cl,
+                       n_post, n_enc, coef, z, x_t, B0, n_gen, C, hw);
+    ALDM_LAUNCH_CHECK("aldm_posterior_qsample");
+    return 0;
+}
+
 extern "C" int aldm_ddpm_step(const float* x, const float* eps, const float* noise, const float* coef,
                               float* x_prev, int64_t n, void* stream) {
     ALDM_CHECK(x && eps && noise && coef && x_prev && n > 0, "aldm_ddpm_step: bad args");

@@ -290,6 +290,50 @@ def guidance_table(rows, scale, use_cfg, phi=0.0):
     return coef
 
 
+def check_t_start(t_start, timesteps, schedule_len):
+    """The `t_start=` keyword of the three samplers (the name of `DDIMSampler.decode`'s parameter): None, or the number k of
+    schedule entries to run — indices k-1 ... 0 — from x_T, 1 <= k <= the schedule's length; not together with `timesteps`, whose
+    count goes through the reference's float arithmetic."""
+    if t_start is None:
+        return None
+    if timesteps is not None:
+        raise ValueError(f"t_start={t_start!r} and timesteps={timesteps!r} both name where to start: pass one")
+    if isinstance(t_start, bool) or not isinstance(t_start, (int, np.integer)) or not 1 <= t_start <= schedule_len:
+        raise ValueError(f"t_start must be an integer in [1, {schedule_len}] (the schedule's length), got {t_start!r}")
+    return int(t_start)
+
+
+def sdedit_plan(strength, ddim_steps, alphas_cumprod, num_timesteps):
+    """Pure host function: where an audio-to-audio job (SDEdit: noise the source, then denoise it under the prompt) enters a
+    sampler's schedule -> (t_enc, timestep, sqrt_abar, sqrt_1m_abar).
+
+    t_enc = int(strength * ddim_steps) is the number of steps to run (AudioLDM's `transfer_strength` rule); strength must lie in
+    (0, 1] and t_enc must be >= 1.  The run executes schedule indices t_enc-1 ... 0, and its first step takes its input to be at
+    the noise level of index t_enc-1: `timestep` = make_ddim_timesteps("uniform", ddim_steps, num_timesteps)[t_enc - 1], and the
+    source is noised to exactly that level, x_t = sqrt_abar * z + sqrt_1m_abar * noise with abar = alphas_cumprod[timestep].  The
+    well-known img2img scripts noise to index t_enc instead — one level above what their first step assumes, and at strength 1
+    an index past the end of the table; this function does not follow them.  The two coefficients are evaluated in fp64 from
+    `alphas_cumprod` as given and returned as Python floats (the caller rounds them to fp32 once)."""
+    try:
+        s = float(strength)
+    except (TypeError, ValueError):
+        raise ValueError(f"strength must be a number in (0, 1], got {strength!r} (ddim_steps={ddim_steps!r})")
+    if isinstance(ddim_steps, bool) or not isinstance(ddim_steps, (int, np.integer)) or ddim_steps < 1:
+        raise ValueError(f"ddim_steps must be a positive integer, got {ddim_steps!r} (strength={strength!r})")
+    if not (np.isfinite(s) and 0.0 < s <= 1.0):
+        raise ValueError(f"strength must lie in (0, 1], got strength={strength!r} (ddim_steps={ddim_steps})")
+    t_enc = int(s * int(ddim_steps))
+    if t_enc < 1:
+        raise ValueError(f"strength={strength!r} of ddim_steps={ddim_steps} leaves int(strength * ddim_steps) = 0 steps to run: "
+                         "raise one of them")
+    ts = make_ddim_timesteps("uniform", int(ddim_steps), int(num_timesteps), verbose=False)
+    t_enc = min(t_enc, len(ts))
+    timestep = int(ts[t_enc - 1])
+    ac = alphas_cumprod.detach().cpu().numpy() if torch.is_tensor(alphas_cumprod) else np.asarray(alphas_cumprod)
+    abar = float(np.asarray(ac, dtype=np.float64)[timestep])
+    return t_enc, timestep, float(np.sqrt(abar)), float(np.sqrt(1.0 - abar))
+
+
 class DDIMSampler(object):
     def __init__(self, model, schedule="linear", device=torch.device("cuda"), **kwargs):
         super().__init__()
@@ -333,20 +377,23 @@ class DDIMSampler(object):
                img_callback=None, quantize_x0=False, eta=0.0, mask=None, x0=None, temperature=1.0,
                noise_dropout=0.0, score_corrector=None, corrector_kwargs=None, verbose=True, x_T=None,
                log_every_t=100, unconditional_guidance_scale=1.0, unconditional_conditioning=None,
-               dynamic_threshold=None, ucg_schedule=None, guidance_rescale=0.0, **kwargs):
-        """ddim.py:94-163, plus `guidance_rescale` (phi of Lin et al. 2023; 0: off — the reference's step)"""
+               dynamic_threshold=None, ucg_schedule=None, guidance_rescale=0.0, t_start=None, **kwargs):
+        """ddim.py:94-163, plus `guidance_rescale` (phi of Lin et al. 2023; 0: off — the reference's step) and `t_start` (None: the
+        whole schedule; k: its first k entries, indices k-1 ... 0, from x_T — see check_t_start)"""
         guidance_rescale = check_guidance_rescale(guidance_rescale)
         if quantize_x0 or score_corrector is not None or dynamic_threshold is not None \
                 or noise_dropout != 0.0 or ucg_schedule is not None:
             raise NotImplementedError("DDIMSampler(HIP): option not used by the AudioLDM2 pipeline")
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
+        check_t_start(t_start, kwargs.get("timesteps"), len(self.ddim_timesteps))
         C, H, W = shape
         size = (batch_size, C, H, W)
         return self.ddim_sampling(conditioning, size, callback=callback, img_callback=img_callback,
                                   mask=mask, x0=x0, temperature=temperature, x_T=x_T,
                                   log_every_t=log_every_t,
                                   unconditional_guidance_scale=unconditional_guidance_scale,
-                                  unconditional_conditioning=unconditional_conditioning, guidance_rescale=guidance_rescale)
+                                  unconditional_conditioning=unconditional_conditioning, guidance_rescale=guidance_rescale,
+                                  t_start=t_start)
 
     # ------------------------------------------------------------------------------------------
     def _drawer(self, shape):
@@ -372,8 +419,9 @@ class DDIMSampler(object):
                       timesteps=None, quantize_denoised=False, mask=None, x0=None, img_callback=None,
                       log_every_t=100, temperature=1.0, noise_dropout=0.0, score_corrector=None,
                       corrector_kwargs=None, unconditional_guidance_scale=1.0,
-                      unconditional_conditioning=None, dynamic_threshold=None, ucg_schedule=None, guidance_rescale=0.0):
-        """ddim.py:166-262"""
+                      unconditional_conditioning=None, dynamic_threshold=None, ucg_schedule=None, guidance_rescale=0.0,
+                      t_start=None):
+        """ddim.py:166-262; `t_start=k`: run exactly the schedule's first k entries (check_t_start)"""
         guidance_rescale = check_guidance_rescale(guidance_rescale)
         if ddim_use_original_steps:
             # the reference's own p_sample_ddim reads `self.model.ddim_sigmas_for_original_num_steps` here (ddim.py:324-327), a
@@ -384,12 +432,15 @@ class DDIMSampler(object):
         dev = torch.device("cuda")
         b = shape[0]
         ts = self.ddim_timesteps
+        t_start = check_t_start(t_start, timesteps, ts.shape[0])
+        if t_start is not None:
+            ts = ts[:t_start]   # as `decode` cuts it (ddim.py:466-467)
         if timesteps is not None:
             # ddim.py:198-206: sample only the first `subset_end` entries of the DDIM sequence (start from a less noisy state)
             subset_end = int(min(timesteps / ts.shape[0], 1) * ts.shape[0]) - 1
             ts = ts[:subset_end]
         total_steps = ts.shape[0]
-        time_range = np.flip(ts)
+        time_range = np.flip(ts).copy()   # own storage, positive strides: from_numpy refuses the flipped view, even of one entry
         use_cfg = not (unconditional_conditioning is None or unconditional_guidance_scale == 1.0)
         if total_steps == 0:
             # `timesteps` <= one DDIM interval: the reference's loop runs zero iterations and returns x_T (ddim.py:198-262)
@@ -399,8 +450,8 @@ class DDIMSampler(object):
         # RNG contract R: x_T first, then the per-step draws, all from the host generator in the
         # reference's order; the per-step draws are streamed (see _NoiseFeed)
         draw = self._drawer(tuple(shape))
-        img_h = draw() if x_T is None else x_T.detach().float().cpu()
-        img = img_h.to(dev).contiguous()
+        # a start latent that already lives on the device (audio-to-audio) stays there
+        img = (draw().to(dev) if x_T is None else x_T.detach().float().to(dev)).contiguous()
         # device tables in loop order (i = 0 is the noisiest step, index = total_steps - 1)
         order = [total_steps - i - 1 for i in range(total_steps)]
         # guidance rescale: the combine and the per-sample rescale run in a launch of their own in front of the step kernel

@@ -35,7 +35,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .ddim import (GraphStepper, check_guidance_rescale, guidance_table, host_drawer, make_ddim_sampling_parameters,
+from .ddim import (GraphStepper, check_guidance_rescale, check_t_start, guidance_table, host_drawer, make_ddim_sampling_parameters,
                    make_ddim_timesteps)
 
 LOWER_ORDER_FINAL_BELOW = 15   # runs shorter than this take their last step at first order
@@ -73,6 +73,7 @@ class DPMSolverSampler(object):
         # phi of Lin et al. 2023 (section 3.4), 0: off.  Sampler state, as in PLMSSampler, whose parameter lists this class
         # carries: `sample` sets it on every call from its `guidance_rescale=` keyword (absent: 0), `dpm_sampling` reads it.
         self.guidance_rescale = 0.0
+        self.t_start = None   # the same way: `sample` sets it from its `t_start=` keyword (absent: None), `dpm_sampling` reads it
 
     def register_buffer(self, name, attr):
         setattr(self, name, attr)
@@ -109,6 +110,9 @@ class DPMSolverSampler(object):
         **kwargs, as there, and becomes `self.guidance_rescale` for this run."""
         self.guidance_rescale = check_guidance_rescale(kwargs.pop("guidance_rescale", 0.0))
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
+        # `t_start` (None or absent: the whole schedule; k: its first k entries, indices k-1 ... 0, from x_T) is read from **kwargs
+        # like `guidance_rescale`, and becomes `self.t_start` for this run
+        self.t_start = check_t_start(kwargs.pop("t_start", None), kwargs.get("timesteps"), len(self.ddim_timesteps))
         C, H, W = shape
         size = (batch_size, C, H, W)
         return self.dpm_sampling(conditioning, size, callback=callback, img_callback=img_callback,
@@ -149,6 +153,9 @@ class DPMSolverSampler(object):
         shape = tuple(shape)
         b = shape[0]
         ts = self.ddim_timesteps
+        t_start = check_t_start(self.t_start, timesteps, ts.shape[0])
+        if t_start is not None:
+            ts = ts[:t_start]   # exactly the schedule's first t_start entries, indices t_start-1 ... 0, from x_T
         if timesteps is not None:
             # as DDIM and PLMS: sample only the first `subset_end` entries of the sequence (start from a less noisy state)
             subset_end = int(min(timesteps / ts.shape[0], 1) * ts.shape[0]) - 1
@@ -158,7 +165,8 @@ class DPMSolverSampler(object):
         use_cfg = not (unconditional_conditioning is None or unconditional_guidance_scale == 1.0)
         # the host generator: x_T first, then (inpainting only) one q_sample draw per step — nothing else
         draw = host_drawer(shape, self.noise_shard)
-        img = (draw() if x_T is None else x_T.detach().float().cpu()).to(dev).contiguous()
+        # a start latent that already lives on the device (audio-to-audio) stays there
+        img = (draw().to(dev) if x_T is None else x_T.detach().float().to(dev)).contiguous()
         intermediates = {"x_inter": [img], "pred_x0": [img]}
         if total_steps == 0:
             # `timesteps` <= one interval: the loop runs zero iterations and returns x_T

@@ -1553,6 +1553,48 @@ def inpaint_blend(x: torch.Tensor, x0: torch.Tensor, qnoise: torch.Tensor, mask:
     return x
 
 
+def posterior_qsample(moments_cl: torch.Tensor, n_post: torch.Tensor, n_enc: torch.Tensor, coef: torch.Tensor,
+                      z: Optional[torch.Tensor] = None, x_t: Optional[torch.Tensor] = None):
+    """The VAE posterior sample and its forward diffusion in one launch (aldm_posterior_qsample): moments_cl [B0, h, w, 2C]
+    channels-last (AutoencoderKL.encode_moments_cl), n_post [B0, C, h, w], n_enc [B0*n_gen, C, h, w], coef = device
+    {scale_factor, sqrt(abar), sqrt(1 - abar)} -> (z [B0, C, h, w] = scale*(mean + std*n_post), x_t [B0*n_gen, C, h, w] =
+    sqrt(abar)*z[r % B0] + sqrt(1 - abar)*n_enc[r]), both NCHW; `z` / `x_t`: write into these (they may overlap neither an
+    input nor each other)."""
+    if moments_cl.dim() != 4 or n_post.dim() != 4 or moments_cl.shape[3] != 2 * n_post.shape[1] \
+            or (moments_cl.shape[0],) + tuple(moments_cl.shape[1:3]) != (n_post.shape[0],) + tuple(n_post.shape[2:]):
+        raise RuntimeError(f"posterior_qsample: moments_cl must be [B0, h, w, 2C] and n_post [B0, C, h, w], got "
+                           f"{tuple(moments_cl.shape)} and {tuple(n_post.shape)}")
+    B0, C, h, w = n_post.shape
+    if n_enc.dim() != 4 or tuple(n_enc.shape[1:]) != (C, h, w) or n_enc.shape[0] == 0 or n_enc.shape[0] % B0 != 0:
+        raise RuntimeError(f"posterior_qsample: n_enc must be [B0*n_gen, C, h, w] = [{B0}*n_gen, {C}, {h}, {w}], got "
+                           f"{tuple(n_enc.shape)}")
+    if coef.numel() < 3:
+        raise RuntimeError(f"posterior_qsample.coef: expected 3 floats, got {coef.numel()}")
+    for t, n, like in ((z, "z", n_post), (x_t, "x_t", n_enc)):
+        if t is not None and tuple(t.shape) != tuple(like.shape):
+            raise RuntimeError(f"posterior_qsample.{n}: expected {tuple(like.shape)}, got {tuple(t.shape)}")
+    for t, n in ((moments_cl, "moments_cl"), (n_post, "n_post"), (n_enc, "n_enc"), (coef, "coef")):
+        _chk(t, "posterior_qsample." + n)
+    if z is None:
+        z = torch.empty_like(n_post)
+    if x_t is None:
+        x_t = torch.empty_like(n_enc)
+    _chk(z, "posterior_qsample.z"); _chk(x_t, "posterior_qsample.x_t")
+    # the kernel reads every operand through a __restrict__ pointer: an output may share no byte with an input or the other output
+    span = lambda t: (t.data_ptr(), t.data_ptr() + 4 * t.numel())
+    others = [(moments_cl, "moments_cl"), (n_post, "n_post"), (n_enc, "n_enc"), (coef, "coef")]
+    for out, n in ((z, "z"), (x_t, "x_t")):
+        for t, m in others:
+            (a0, a1), (b0, b1) = span(out), span(t)
+            if a0 < b1 and b0 < a1:
+                raise RuntimeError(f"posterior_qsample.{n} overlaps {m}: the outputs must not alias an operand")
+        others.append((out, n))
+    _l.check(_l.load().aldm_posterior_qsample(moments_cl.data_ptr(), n_post.data_ptr(), n_enc.data_ptr(), coef.data_ptr(),
+                                              z.data_ptr(), x_t.data_ptr(), B0, n_enc.shape[0] // B0, C, h * w, _stream()),
+             "posterior_qsample")
+    return z, x_t
+
+
 def axpby(a: torch.Tensor, b: Optional[torch.Tensor], alpha: float, beta: float = 0.0,
           out: Optional[torch.Tensor] = None) -> torch.Tensor:
     _chk(a, "axpby.a")

@@ -578,8 +578,19 @@ class LatentDiffusion(nn.Module):
             kwargs.pop("guidance_rescale", None)   # off: today's call, unchanged
         elif not (use_plms or sampler_name is not None or ddim):
             raise ValueError("guidance_rescale needs ddim_steps: the ancestral sampler has no guidance")
+        # `t_start` (a keyword of **kwargs: run only the schedule's first t_start entries from x_T) goes to whichever of the three
+        # samplers runs; the start latent then sets the shape
+        t_start = kwargs.get("t_start", None)
+        if t_start is None:
+            kwargs.pop("t_start", None)   # absent: today's call, unchanged
+        elif not (use_plms or sampler_name is not None or ddim):
+            raise ValueError("t_start needs ddim_steps: the ancestral sampler has no such schedule")
+        elif kwargs.get("x_T", None) is None:
+            raise ValueError("t_start needs x_T: the latent the shortened run starts from")
         if mask is not None:
             shape = (self.channels, mask.size()[-2], mask.size()[-1])
+        elif t_start is not None:
+            shape = tuple(kwargs["x_T"].shape[1:])
         else:
             shape = (self.channels, self.latent_t_size, self.latent_f_size)
         if use_plms:
@@ -935,6 +946,72 @@ class LatentDiffusion(nn.Module):
         return waveform
 
 
+    @torch.no_grad()
+    def generate_batch_from_audio(self, batch, strength, ddim_steps=200, ddim_eta=1.0, n_gen=1,
+                                  unconditional_guidance_scale=1.0, use_plms=False, **kwargs):
+        """Audio-to-audio (SDEdit; the "style transfer" of the first AudioLDM): VAE-encode the mel of `batch["log_mel_spec"]`
+        [B0, T, F], noise the scaled posterior sample to the level the sampler's step t_enc-1 expects (ddim.sdedit_plan: t_enc =
+        int(strength * ddim_steps), strength in (0, 1]) and run the last t_enc steps under the prompt.  `sampler`,
+        `negative_prompt` and `guidance_rescale` travel in **kwargs as in generate_batch_masked.  The posterior sample and the
+        forward diffusion are one launch on the encoder's channels-last moments (ops.posterior_qsample); every sampler runs
+        its usual step graph from the start latent (`x_T=`, `t_start=t_enc`).
+
+        Host-generator order (RNG contract): (R1) randn(B0, C, h, w), the posterior noise — the masked path's
+        draw; (R1b) the rand(1) of _cfg_dropout_draw on every call but an object's first; the conditioners' draws (twice with a
+        negative prompt); randn(B0*n_gen, C, h, w), the forward-diffusion noise, in the place of the x_T draw; the sampler's
+        per-step draws for t_enc steps."""
+        from .ddim import sdedit_plan
+        if kwargs.get("shard", None) is not None:
+            raise ValueError("generate_batch_from_audio: shard= is not supported on this path")
+        if ddim_steps is None:
+            raise ValueError("generate_batch_from_audio needs ddim_steps: the ancestral sampler has no shortened schedule")
+        sampler = resolve_sampler(kwargs.get("sampler", None), use_plms)
+        neg_batch, guidance_rescale = _guidance_kwargs(kwargs, unconditional_guidance_scale, batch, ddim_steps)
+        t_enc, _, sa, so = sdedit_plan(strength, ddim_steps, self.alphas_cumprod, self.num_timesteps)
+        self._check_candidates(n_gen, batch.get("text"))
+        fb = batch["log_mel_spec"] if self.first_stage_key == "fbank" else batch[self.first_stage_key]
+        self.check_latent_t(fb.shape[-2] // 2 ** (self.first_stage_model.encoder.num_resolutions - 1))
+        x = fb.unsqueeze(1).float().contiguous().to(self.device)  # DDPM.get_input: [B, 1, T, F]
+        moments = self.first_stage_model.encode_moments_cl(x)     # [B0, h, w, 2C] channels-last
+        B0, h, w, C = moments.shape[0], moments.shape[1], moments.shape[2], moments.shape[3] // 2
+        n_post = torch.randn((B0, C, h, w))                        # (R1) the posterior draw
+        self._cfg_dropout_draw()                                   # (R1b) every call but the first
+        c = self.get_learned_conditioning_dict(batch)
+        batch_size = B0 * n_gen
+        c = _tile_cond(c, n_gen)
+        text = list(batch["text"]) * n_gen
+        unconditional_conditioning = None
+        if neg_batch is not None:
+            # the negative prompt's conditioning is the unconditional half: a second conditioner pass, after the positive one
+            unconditional_conditioning = _tile_cond(self.get_learned_conditioning_dict(neg_batch), n_gen)
+        elif unconditional_guidance_scale != 1.0:
+            unconditional_conditioning = {}
+            for key, meta in self.cond_stage_model_metadata.items():
+                unconditional_conditioning[key] = self.cond_stage_models[
+                    meta["model_idx"]].get_unconditional_condition(batch_size)
+        n_enc = torch.randn((batch_size, C, h, w))                 # the forward-diffusion noise, in the place of the x_T draw
+        # {scale_factor, sqrt(abar), sqrt(1 - abar)} on the device; a scale_factor buffer is read where it lives (no host round trip)
+        coef = torch.tensor([1.0 if torch.is_tensor(self.scale_factor) else float(self.scale_factor), sa, so],
+                            dtype=torch.float32).to(self.device)
+        if torch.is_tensor(self.scale_factor):
+            coef[0:1].copy_(self.scale_factor.detach().reshape(1))
+        _, x_t = ops.posterior_qsample(moments, n_post.to(self.device), n_enc.to(self.device), coef)
+        samples, _ = self.sample_log(cond=c, batch_size=batch_size, x_T=x_t, t_start=t_enc, ddim=True, ddim_steps=ddim_steps,
+                                     eta=ddim_eta, unconditional_guidance_scale=unconditional_guidance_scale,
+                                     unconditional_conditioning=unconditional_conditioning, use_plms=use_plms,
+                                     **({} if sampler is None else {"sampler": sampler}),
+                                     **({} if guidance_rescale == 0.0 else {"guidance_rescale": guidance_rescale}))
+        mel = self.decode_first_stage_cl(samples)
+        waveform = self.mel_spectrogram_to_waveform(mel.view(mel.shape[0], mel.shape[1], mel.shape[2]),
+                                                    savepath="", bs=None, name=batch.get("fname"), save=False)
+        if n_gen > 1:
+            similarity = self.clap.cos_similarity(torch.FloatTensor(waveform).squeeze(1), text)   # ddpm.py:1660-1670
+            best = [i + torch.argmax(similarity[i::B0]).item() * B0 for i in range(B0)]
+            waveform = waveform[best]
+            self.last_similarity, self.last_best_index = similarity.detach().cpu(), best
+        return waveform
+
+
 # ------------------------------------------------------------------------------------------------
 # The reference turns a transcription into an IPA string with phonemizer / espeak (`text2phoneme`, pipeline.py:33-34: a text
 # front end like the tokenizers, not installed here).  Set this to a callable(text) -> IPA string to use the speech models
@@ -1183,3 +1260,34 @@ def text_to_audio(latent_diffusion, text, transcription="", seed=42, ddim_steps=
         return latent_diffusion.generate_batch(batch, unconditional_guidance_scale=guidance_scale,
                                                ddim_steps=ddim_steps, n_gen=n_candidate_gen_per_text,
                                                duration=duration, **sampler_kw)
+
+
+def audio_to_audio(latent_diffusion, text, original_audio_file_path, strength=0.5, transcription="", seed=42,
+                   ddim_steps=200, duration=10, batchsize=1, guidance_scale=3.5, n_candidate_gen_per_text=3,
+                   latent_t_per_second=25.6, negative_prompt=None, guidance_rescale=0.0, sampler=None):
+    """Audio-to-audio generation: a variation of the clip `original_audio_file_path` (a path, or a 1-D float waveform at 16 kHz;
+    cut or zero-padded to `duration` seconds) under the prompt `text`.  `strength` in (0, 1] says how far to move from the
+    source: the clip's latent is noised to the level of step int(strength * ddim_steps) - 1 of the `ddim_steps` schedule and
+    that many steps are run (LatentDiffusion.generate_batch_from_audio); at strength 1 nothing of the source survives but the
+    noise it was mixed into.  `negative_prompt`, `guidance_rescale` and `sampler` as in text_to_audio.  The front end is
+    super_resolution_and_inpainting's (wav_to_fbank, the 16 kHz TacotronSTFT): a model whose first stage is not 16 kHz /
+    64 mel bins is refused.  Returns np.float32 [batchsize, 1, samples]."""
+    from .ddim import sdedit_plan
+    from .stft import TacotronSTFT
+    sampler_kw = _sampler_kwargs(sampler, negative_prompt, guidance_rescale)
+    sdedit_plan(strength, ddim_steps, latent_diffusion.alphas_cumprod, latent_diffusion.num_timesteps)   # refuse before any GPU work
+    mel_bins = int(latent_diffusion.latent_f_size) * 2 ** (latent_diffusion.first_stage_model.encoder.num_resolutions - 1)
+    if int(latent_diffusion.sampling_rate) != 16000 or mel_bins != 64:
+        raise ValueError("audio_to_audio: the mel front end is the 16 kHz / 64-bin one; this model's first stage takes "
+                         f"{latent_diffusion.sampling_rate} Hz / {mel_bins} bins")
+    seed_everything(int(seed))
+    latent_diffusion.latent_t_size = int(duration * latent_t_per_second)
+    LatentDiffusion.check_latent_t(latent_diffusion.latent_t_size)
+    fn_STFT = TacotronSTFT(1024, 160, 1024, 64, 16000, 0, 8000)  # utils.py:262-270 "preprocessing"
+    mel, _, _ = wav_to_fbank(original_audio_file_path, target_length=int(duration * 102.4), fn_STFT=fn_STFT)
+    batch = make_batch_for_text_to_audio(text, transcription=transcription, fbank=mel[None, ...].numpy(),
+                                         batchsize=batchsize)
+    with torch.no_grad():
+        return latent_diffusion.generate_batch_from_audio(
+            batch, strength, unconditional_guidance_scale=guidance_scale, ddim_steps=ddim_steps,
+            n_gen=n_candidate_gen_per_text, duration=duration, **sampler_kw)

@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .ddim import (GraphStepper, check_guidance_rescale, guidance_table, host_drawer, make_ddim_sampling_parameters,
+from .ddim import (GraphStepper, check_guidance_rescale, check_t_start, guidance_table, host_drawer, make_ddim_sampling_parameters,
                    make_ddim_timesteps)
 
 
@@ -41,6 +41,7 @@ class PLMSSampler(object):
         self.use_graph = os.environ.get("ALDM_NO_GRAPH", "0") != "1"
         # (global_batch, row_offset) when this process samples one shard of a larger batch (dist.py)
         self.noise_shard = getattr(model, "noise_shard", None)
+        self.t_start = None   # sampler state like guidance_rescale: `sample` sets it on every call, `plms_sampling` reads it
         # phi of Lin et al. 2023 (section 3.4), 0: off.  Sampler state like the schedule, not a parameter: `plms_sampling` and
         # `p_sample_plms` keep the reference class's signatures, which have no **kwargs to take it.  `sample` sets it on every
         # call from its `guidance_rescale=` keyword (absent: 0); a caller of the two other methods sets the attribute.
@@ -84,6 +85,9 @@ class PLMSSampler(object):
         **kwargs, so the signature stays the reference's, and becomes `self.guidance_rescale` for this run"""
         self.guidance_rescale = check_guidance_rescale(kwargs.pop("guidance_rescale", 0.0))
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
+        # `t_start` (None or absent: the whole schedule; k: its first k entries, indices k-1 ... 0, from x_T) is read from **kwargs
+        # like `guidance_rescale`, and becomes `self.t_start` for this run
+        self.t_start = check_t_start(kwargs.pop("t_start", None), kwargs.get("timesteps"), len(self.ddim_timesteps))
         C, H, W = shape
         size = (batch_size, C, H, W)
         return self.plms_sampling(conditioning, size, callback=callback, img_callback=img_callback,
@@ -127,6 +131,9 @@ class PLMSSampler(object):
         shape = tuple(shape)
         b = shape[0]
         ts = self.ddim_timesteps
+        t_start = check_t_start(self.t_start, timesteps, ts.shape[0])
+        if t_start is not None:
+            ts = ts[:t_start]   # exactly the schedule's first t_start entries, indices t_start-1 ... 0, from x_T
         if timesteps is not None:
             # plms.py:190-198: sample only the first `subset_end` entries of the sequence (start from a less noisy state)
             subset_end = int(min(timesteps / ts.shape[0], 1) * ts.shape[0]) - 1
@@ -136,7 +143,8 @@ class PLMSSampler(object):
         use_cfg = not (unconditional_conditioning is None or unconditional_guidance_scale == 1.0)
         # RNG contract R: x_T first, then the per-step draws, all from the host generator on this thread in the reference's order
         draw = host_drawer(shape, self.noise_shard)
-        img = (draw() if x_T is None else x_T.detach().float().cpu()).to(dev).contiguous()
+        # a start latent that already lives on the device (audio-to-audio) stays there
+        img = (draw().to(dev) if x_T is None else x_T.detach().float().to(dev)).contiguous()
         intermediates = {"x_inter": [img], "pred_x0": [img]}
         if total_steps == 0:
             # `timesteps` <= one interval: the reference's loop runs zero iterations and returns x_T

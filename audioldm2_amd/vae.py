@@ -345,7 +345,14 @@ class AutoencoderKL(nn.Module):
         """autoencoder.py:103-109: x [B, 1, T, F] -> posterior over [B, zc, T/4, F/4]."""
         if not x.is_cuda:
             raise RuntimeError("AutoencoderKL(HIP) runs on the MI355X only; there is no CPU path")
+        return DiagonalGaussianDistribution(ops.nhwc_to_nchw(self.encode_moments_cl(x)))
+
+    @torch.no_grad()
+    def encode_moments_cl(self, x: torch.Tensor) -> torch.Tensor:
+        """x [B, 1, T, F] -> the posterior's moments, channels-last [B, T/4, F/4, 2*embed_dim]: mean in channels 0..embed_dim-1,
+        logvar behind it — what `encode` transposes to NCHW, and what ops.posterior_qsample reads as it is."""
+        if not x.is_cuda:
+            raise RuntimeError("AutoencoderKL(HIP) runs on the MI355X only; there is no CPU path")
         pk = self._prepare()
         h = self.encoder.run(ops.nchw_to_nhwc(x.float().contiguous()))
-        moments = ops.conv(h, pk["quant"])
-        return DiagonalGaussianDistribution(ops.nhwc_to_nchw(moments))
+        return ops.conv(h, pk["quant"])

@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 /* ---- library / error ------------------------------------------------------------------ */
-int aldm_version(void);              /* ABI version (15), bumped on any struct / entry change */
+int aldm_version(void);              /* ABI version (16), bumped on any struct / entry change */
 const char* aldm_last_error(void);   /* message of the last failing call on this thread     */
 
 /* ---- activations usable as prologue (applied to the gathered input) or epilogue -------- */
@@ -530,6 +530,17 @@ int aldm_ddpm_step(const float* x, const float* eps, const float* noise, const f
  *   x = (sa*x0 + so*qnoise)*mask + (1 - mask)*x,  coef (device) = {sqrt(abar_t), sqrt(1 - abar_t)} */
 int aldm_inpaint_blend(const float* x0, const float* qnoise, const float* mask, const float* coef,
                        float* x, int64_t n, void* stream);
+/* VAE posterior sample fused with the forward diffusion to the sampler's first noise level (audio-to-audio; ABI v16): one launch
+ * from the encoder's channels-last moments (autoencoder.py:103-109, distributions.py:24-41, ddpm.py:793-802, ddim.py:434-449):
+ *   moments_cl [B0, hw, 2C] channels-last: mean = channels 0..C-1, logvar = channels C..2C-1
+ *   n_post [B0, C, hw] NCHW, the posterior noise;  n_enc [B0*n_gen, C, hw] NCHW, the forward-diffusion noise
+ *   coef (device) = {scale_factor, sqrt(abar), sqrt(1 - abar)}
+ *   lv = clamp(logvar, -30, 20); std = expf(0.5f*lv); z = scale*(mean + std*n_post); x_t[r] = sqrt(abar)*z[r % B0] + sqrt(1 - abar)*n_enc[r]
+ * z [B0, C, hw] and x_t [B0*n_gen, C, hw] are NCHW; rows of x_t are candidate-major (torch.cat([z]*n_gen)).  A NaN logvar stays NaN
+ * (torch.clamp's behaviour), +-inf clamp to 20 / -30.  C % 4 == 0, moments_cl 16-byte aligned; bad arguments are refused before
+ * the launch.                                                                                                                    */
+int aldm_posterior_qsample(const float* moments_cl, const float* n_post, const float* n_enc, const float* coef, float* z,
+                           float* x_t, int B0, int n_gen, int C, int64_t hw, void* stream);
 /* generic y = alpha*a + beta*b (b may be NULL) */
 int aldm_axpby(const float* a, const float* b, float* y, float alpha, float beta, int64_t n,
                void* stream);
