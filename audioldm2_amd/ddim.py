@@ -12,295 +12,24 @@ Differences that matter on MI355X:
   * RNG contract: x_T and the per-step noise are drawn from the HOST CPU
     generator in the reference's order and shapes (ddim.py:191,351 via util.py:289-294), uploaded
     once — results match the CPU reference on the same seed.
+
+What this class shares with PLMSSampler and DPMSolverSampler (the schedule, the run plan, the UNet pass of a step, the graph
+stepper, the noise feed) is in sampling.py; here are DDIM's coefficient rows, its step closure, the graph cache on the UNet and the
+threaded noise feed of its loop, the eager single-step methods, and sdedit_plan.
 """
 from __future__ import annotations
 
-import gc
 import os
 
 import numpy as np
 import torch
 
 from . import ops
+# the samplers' shared core; every name below lived in this module before sampling.py existed and is still exported from here
+from .sampling import (GraphStepper, SamplerBase, _NoiseFeed, check_guidance_rescale, check_t_start,  # noqa: F401
+                       ddim_step_rows, drop_graph_entries, guidance_table, host_drawer, log_step, make_ddim_sampling_parameters,
+                       make_ddim_timesteps)
 
-
-def make_ddim_timesteps(ddim_discr_method, num_ddim_timesteps, num_ddpm_timesteps, verbose=True):
-    """util.py:55-75"""
-    if ddim_discr_method == "uniform":
-        c = num_ddpm_timesteps // num_ddim_timesteps
-        ddim_timesteps = np.asarray(list(range(0, num_ddpm_timesteps, c)))
-    elif ddim_discr_method == "quad":
-        ddim_timesteps = ((np.linspace(0, np.sqrt(num_ddpm_timesteps * 0.8), num_ddim_timesteps)) ** 2).astype(int)
-    else:
-        raise NotImplementedError(f'There is no ddim discretization method called "{ddim_discr_method}"')
-    return ddim_timesteps + 1
-
-
-def make_ddim_sampling_parameters(alphacums, ddim_timesteps, eta, verbose=True):
-    """util.py:78-95 — keeps the reference's mixed float32-tensor / float64-ndarray arithmetic:
-    (1 - alphas) is a float32 tensor op, the rest float64."""
-    alphas = alphacums[ddim_timesteps]
-    alphas_prev = np.asarray([alphacums[0]] + alphacums[ddim_timesteps[:-1]].tolist())
-    sigmas = eta * np.sqrt((1 - alphas_prev) / (1 - alphas) * (1 - alphas / alphas_prev))
-    return torch.as_tensor(np.asarray(sigmas, dtype=np.float64)), alphas, alphas_prev
-
-
-class GraphStepper:
-    """Runs a fixed launch sequence repeatedly: eagerly the first time (packs weights, warms the
-    allocator, grows the split-K workspace), captured into a HIP graph the second time, replayed after.
-    The callable must read its per-step inputs from static device buffers."""
-
-    def __init__(self, fn, use_graph=True):
-        self.fn, self.use_graph, self.calls, self.graph = fn, use_graph, 0, None
-
-    def __call__(self):
-        if self.use_graph and self.calls >= 1:
-            if self.graph is None:
-                g = torch.cuda.CUDAGraph()
-                torch.cuda.synchronize()
-                # No cyclic garbage collection while the stream is capturing: a collection that happens to run inside the
-                # capture can finalise objects of EARLIER jobs (an evicted step graph, a noise feed's side stream and pinned
-                # buffers) whose destructors call HIP functions that are illegal during capture — the C++ destructor then
-                # throws and the process aborts ("Fatal Python error: Aborted ... Garbage-collecting" a few tests into a
-                # long session, at a different place every time).  Collect first, then hold the collector off.
-                gc.collect()
-                gc_was_on = gc.isenabled()
-                gc.disable()
-                try:
-                    # thread_local: other threads (e.g. the RCCL watchdog of a multi-GPU run) may keep
-                    # calling HIP while this thread captures
-                    with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                        self.fn()
-                    self.graph = g
-                except RuntimeError as e:  # capture refused: keep sampling eagerly, say so once
-                    import sys
-                    print(f"[audioldm2_amd] HIP graph capture failed ({e}); continuing without a graph",
-                          file=sys.stderr, flush=True)
-                    self.use_graph = False
-                    torch.cuda.synchronize()
-                    if gc_was_on:
-                        gc.enable()
-                    self.fn()
-                    self.calls += 1
-                    return
-                finally:
-                    if gc_was_on:
-                        gc.enable()
-            self.graph.replay()
-        else:
-            self.fn()
-        self.calls += 1
-
-
-def drop_graph_entries(cache: dict) -> None:
-    """Evict cached step graphs NOW, by reference counting: an entry is a reference cycle (entry -> stepper -> step closure ->
-    entry), so simply forgetting it leaves the HIP graph, its private memory pool and its static buffers to the cyclic
-    collector — which may then run in the middle of the next capture (see GraphStepper).  Breaking the cycle here frees
-    them at a point where no stream is capturing."""
-    for ent in list(cache.values()):
-        rs = ent.get("run_step")
-        if rs is not None:
-            rs.fn = None
-            rs.graph = None
-        ent.clear()
-    cache.clear()
-
-
-class _NoiseFeed:
-    """Streams the per-step host noise to the GPU in chunks.  A DRAWER THREAD consumes the CPU generator (the reference's RNG
-    stream, strictly in its order: only this thread draws while a sampling run is in flight) into pinned staging rows and
-    issues the PCIe uploads on a side stream, running up to `len(pin)` chunks ahead of the GPU; the launching thread only
-    makes its stream wait for a chunk's upload event (`wait(i)`).  Round 2 drew on the launching thread between graph replays:
-    with prompt sharding every rank draws the GLOBAL batch (7 ms per step at 8 ranks x 8 prompts against a 16 ms GPU step,
-    profiles/r02_host_noise_cost.txt) — one kernel speed-up away from bounding the job.  `torch.randn` releases the GIL.
-    Device buffers hold all steps (`noise_buf` / `qnoise_buf`: write into these — the static inputs of a cached step graph —
-    instead of allocating); `close()` joins the thread: after it the generator is where the reference leaves it."""
-
-    def __init__(self, draw, steps, shape, with_mask, temperature, dev, chunk=8, mask_first=True, noise_buf=None,
-                 qnoise_buf=None, threaded=None):
-        import threading
-        self.draw, self.steps, self.with_mask, self.temperature = draw, steps, with_mask, temperature
-        self.mask_first = mask_first  # DDIM draws the q_sample noise before the step noise, DDPM after
-        # chunk boundaries: the first chunk is ONE step so the GPU starts right away, then `chunk` steps
-        self.bounds = [0, min(1, steps)]
-        while self.bounds[-1] < steps:
-            self.bounds.append(min(steps, self.bounds[-1] + chunk))
-        self.chunk = chunk
-        self.noise = noise_buf if noise_buf is not None else torch.empty((steps,) + tuple(shape), device=dev,
-                                                                         dtype=torch.float32)
-        assert self.noise.shape == (steps,) + tuple(shape)
-        self.qnoise = (qnoise_buf if qnoise_buf is not None else torch.empty_like(self.noise)) if with_mask else None
-        nbuf = 3
-        self.pin = [torch.empty((chunk,) + tuple(shape)).pin_memory() for _ in range(nbuf)]
-        self.qpin = [torch.empty((chunk,) + tuple(shape)).pin_memory() for _ in range(nbuf)] if with_mask else None
-        self.stream = torch.cuda.Stream(device=dev)
-        # the device buffers may have been handed out while kernels already queued on the current stream (the previous run's
-        # noise copies / step graph) still read them: the upload stream must not start writing before the current stream has
-        # reached this point
-        self.stream.wait_stream(torch.cuda.current_stream())
-        self.noise.record_stream(self.stream)
-        if self.qnoise is not None:
-            self.qnoise.record_stream(self.stream)
-        self.events = {}
-        self.produced = 0  # chunks drawn so far
-        self.dev_index = torch.cuda.current_device()   # the drawer thread must issue its uploads on THIS device
-        self.error = None
-        self.cv = threading.Condition()
-        self.threaded = (os.environ.get("ALDM_NOISE_THREAD", "1") != "0") if threaded is None else threaded
-        self.thread = None
-        if self.threaded:
-            self.thread = threading.Thread(target=self._run, name="aldm-noise-drawer", daemon=True)
-            self.thread.start()
-
-    def _draw_into(self, dst):
-        """One reference-ordered draw into a (pinned) staging row."""
-        d = self.draw
-        if getattr(d, "into", None) is not None:
-            d.into(dst)
-        else:
-            dst.numpy()[...] = d().numpy()   # plain memcpy, no thread pool
-
-    def _produce(self, c):
-        lo, hi = self.bounds[c], self.bounds[c + 1]
-        slot = c % len(self.pin)
-        prev = self.events.get(c - len(self.pin))
-        if prev is not None:
-            prev.synchronize()  # the upload that last used this pinned slot is done
-        # Host side of the RNG contract.  The draws go STRAIGHT into the pinned staging rows (`torch.randn(out=...)`: same
-        # generator stream, no intermediate tensor): a 1 MB `Tensor.copy_` through torch's intra-op thread pool costs
-        # ~20 ms on a many-core host (measured: 19 ms with 8 threads on 8 busy vCPUs vs 0.02 ms with 4).
-        for s in range(lo, hi):  # reference order per step
-            if self.with_mask and self.mask_first:
-                self._draw_into(self.qpin[slot][s - lo])
-            self._draw_into(self.pin[slot][s - lo])
-            if self.temperature != 1.0:
-                self.pin[slot][s - lo].mul_(self.temperature)
-            if self.with_mask and not self.mask_first:
-                self._draw_into(self.qpin[slot][s - lo])
-        with torch.cuda.stream(self.stream):
-            self.noise[lo:hi].copy_(self.pin[slot][:hi - lo], non_blocking=True)
-            if self.with_mask:
-                self.qnoise[lo:hi].copy_(self.qpin[slot][:hi - lo], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(self.stream)
-        return ev
-
-    def _run(self):   # drawer thread
-        try:
-            torch.cuda.set_device(self.dev_index)
-            for c in range(len(self.bounds) - 1):
-                ev = self._produce(c)
-                with self.cv:
-                    self.events[c] = ev
-                    self.produced = c + 1
-                    self.cv.notify_all()
-        except BaseException as e:  # surfaced by the launching thread's next wait()
-            with self.cv:
-                self.error = e
-                self.cv.notify_all()
-
-    def produce_next(self):
-        """Unthreaded mode (ALDM_NOISE_THREAD=0 / tests): draw + upload the next chunk on the calling thread."""
-        if self.threaded:
-            return
-        c = self.produced
-        if c + 1 >= len(self.bounds):
-            return
-        self.events[c] = self._produce(c)
-        self.produced = c + 1
-
-    def wait(self, i):
-        """Make the current stream wait for step i's noise; returns True when i opens a chunk."""
-        c = 0 if i == 0 else 1 + (i - 1) // self.chunk
-        if self.threaded:
-            with self.cv:
-                while self.produced <= c and self.error is None:
-                    self.cv.wait(timeout=60.0)
-                if self.error is not None:
-                    raise RuntimeError(f"noise drawer thread failed: {self.error!r}")
-        else:
-            while self.produced <= c:
-                self.produce_next()
-        first = i == self.bounds[c]
-        if first:
-            torch.cuda.current_stream().wait_event(self.events[c])
-        return first
-
-    def close(self):
-        """Join the drawer: every draw of the run has been consumed from the generator (callers draw again afterwards)."""
-        if self.thread is not None:
-            self.thread.join()
-            self.thread = None
-            if self.error is not None:
-                raise RuntimeError(f"noise drawer thread failed: {self.error!r}")
-
-
-def host_drawer(shape, noise_shard=None):
-    """draw() -> one `torch.randn(shape)` from the host default generator, in the reference's order; draw.into(dst) writes
-    it into `dst`.  noise_shard = (global_batch, row_offset): a prompt-sharded run draws the GLOBAL batch like the
-    single-process reference and keeps rows [offset, offset + shape[0]) (dist.py); with several candidates per prompt
-    the second element is the index tensor of the rank's rows (dist.candidate_rows) instead of an offset."""
-    shape = tuple(shape)
-    if noise_shard is None:
-        def draw():
-            return torch.randn(shape)
-
-        def into(dst):
-            torch.randn(shape, out=dst)
-    else:
-        gB, off = noise_shard
-        gshape = (gB,) + shape[1:]
-        if torch.is_tensor(off):
-            assert off.numel() == shape[0]
-            pick = lambda t: t.index_select(0, off)
-        else:
-            pick = lambda t: t[off:off + shape[0]]
-
-        def draw():
-            return pick(torch.randn(gshape)).contiguous()
-
-        def into(dst):
-            dst.numpy()[...] = pick(torch.randn(gshape)).numpy()
-    draw.into = into
-    return draw
-
-
-def check_guidance_rescale(phi) -> float:
-    """The `guidance_rescale` argument of the samplers and the pipeline as a float: phi of Lin et al. 2023 (section 3.4), in [0, 1];
-    0 is off."""
-    try:
-        phi = float(phi)
-    except (TypeError, ValueError):
-        raise ValueError(f"guidance_rescale must be a number in [0, 1], got {phi!r}")
-    if not (np.isfinite(phi) and 0.0 <= phi <= 1.0):
-        raise ValueError(f"guidance_rescale must be finite and in [0, 1], got {phi!r}")
-    return phi
-
-
-def guidance_table(rows, scale, use_cfg, phi=0.0):
-    """Pure host function: a sampler's [S, 8] fp32 coefficient table from its [S, 5] rows.  Column 5 = the guidance scale; column
-    6 = 1 when the step kernel combines eps[2, n] itself; column 7 = phi.  With guidance rescale on (guidance and phi > 0) the
-    combine moves into ops.cfg_rescale_indexed, which reads columns 5 and 7, and the step kernel gets a combined eps[n]: column 6 = 0."""
-    rescale = bool(use_cfg) and phi > 0.0
-    coef = torch.zeros(rows.shape[0], 8)
-    coef[:, :5] = rows
-    coef[:, 5] = float(scale)
-    coef[:, 6] = 1.0 if use_cfg and not rescale else 0.0
-    coef[:, 7] = float(phi) if rescale else 0.0
-    return coef
-
-
-def check_t_start(t_start, timesteps, schedule_len):
-    """The `t_start=` keyword of the three samplers (the name of `DDIMSampler.decode`'s parameter): None, or the number k of
-    schedule entries to run — indices k-1 ... 0 — from x_T, 1 <= k <= the schedule's length; not together with `timesteps`, whose
-    count goes through the reference's float arithmetic."""
-    if t_start is None:
-        return None
-    if timesteps is not None:
-        raise ValueError(f"t_start={t_start!r} and timesteps={timesteps!r} both name where to start: pass one")
-    if isinstance(t_start, bool) or not isinstance(t_start, (int, np.integer)) or not 1 <= t_start <= schedule_len:
-        raise ValueError(f"t_start must be an integer in [1, {schedule_len}] (the schedule's length), got {t_start!r}")
-    return int(t_start)
 
 
 def sdedit_plan(strength, ddim_steps, alphas_cumprod, num_timesteps):
@@ -334,43 +63,17 @@ def sdedit_plan(strength, ddim_steps, alphas_cumprod, num_timesteps):
     return t_enc, timestep, float(np.sqrt(abar)), float(np.sqrt(1.0 - abar))
 
 
-class DDIMSampler(object):
+class DDIMSampler(SamplerBase):
     def __init__(self, model, schedule="linear", device=torch.device("cuda"), **kwargs):
-        super().__init__()
-        self.model = model
-        self.ddpm_num_timesteps = model.num_timesteps
-        self.schedule = schedule
+        super().__init__(model, schedule)
         self.device = device
-        self.use_graph = os.environ.get("ALDM_NO_GRAPH", "0") != "1"
-        # (global_batch, row_offset) when this process samples one shard of a larger batch (dist.py)
-        self.noise_shard = getattr(model, "noise_shard", None)
-
-    def register_buffer(self, name, attr):
-        setattr(self, name, attr)
 
     def make_schedule(self, ddim_num_steps, ddim_discretize="uniform", ddim_eta=0.0, verbose=True):
         """ddim.py:33-91 (host side, float tables only)."""
-        self.ddim_timesteps = make_ddim_timesteps(ddim_discretize, ddim_num_steps, self.ddpm_num_timesteps, verbose)
-        alphas_cumprod = self.model.alphas_cumprod.detach().float().cpu()
-        assert alphas_cumprod.shape[0] == self.ddpm_num_timesteps, "alphas have to be defined for each timestep"
-        self.alphas_cumprod = alphas_cumprod
-        self.sqrt_alphas_cumprod = torch.sqrt(alphas_cumprod)
-        self.sqrt_one_minus_alphas_cumprod = torch.sqrt(1.0 - alphas_cumprod)
-        sig, a, a_prev = make_ddim_sampling_parameters(alphas_cumprod, self.ddim_timesteps, ddim_eta, verbose)
-        self.ddim_sigmas = sig
-        self.ddim_alphas = a
-        self.ddim_alphas_prev = a_prev
-        self.ddim_sqrt_one_minus_alphas = np.sqrt(1.0 - a.numpy())
-        # per-index coefficient rows with the reference's roundings (ddim.py:330-353): a_t, a_prev,
-        # sigma_t, sqrt(1-a_t) become fp32 via torch.full; the other square roots are fp32 tensor ops.
-        rows = []
-        for i in range(len(self.ddim_timesteps)):
-            a_t = torch.full((1,), float(a[i]))
-            ap = torch.full((1,), float(a_prev[i]))
-            sg = torch.full((1,), float(sig[i]))
-            som = torch.full((1,), float(self.ddim_sqrt_one_minus_alphas[i]))
-            rows.append(torch.cat([som, a_t.sqrt(), (1.0 - ap - sg ** 2).sqrt(), ap.sqrt(), sg]))
-        self.ddim_coef = torch.stack(rows)  # [S, 5] fp32 (host)
+        super().make_schedule(ddim_num_steps, ddim_discretize, ddim_eta, verbose)
+        self.ddim_sqrt_one_minus_alphas = np.sqrt(1.0 - self.ddim_alphas.numpy())
+        self.ddim_coef = ddim_step_rows(self.ddim_sigmas, self.ddim_alphas, self.ddim_alphas_prev,
+                                        self.ddim_sqrt_one_minus_alphas)  # [S, 5] fp32 (host)
 
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None,
@@ -396,16 +99,11 @@ class DDIMSampler(object):
                                   t_start=t_start)
 
     # ------------------------------------------------------------------------------------------
-    def _drawer(self, shape):
-        """One reference-ordered Gaussian draw from the HOST default generator (RNG contract R).  The returned callable
-        also has `.into(dst)`: the same draw written into an existing host tensor."""
-        return host_drawer(shape, self.noise_shard)
-
     def _draw_noise(self, shape, steps, x_T, with_mask):
         """Replays the reference's host RNG order: x_T, then per step [q_sample noise (inpainting
         only, ddim.py:228 / ddpm.py:430-436)], step noise (ddim.py:351).  (Eager form, used by tests;
         ddim_sampling streams the same sequence through _NoiseFeed.)"""
-        draw = self._drawer(shape)
+        draw = host_drawer(shape, self.noise_shard)
         img = draw() if x_T is None else x_T
         step_noise, q_noise = [], []
         for _ in range(steps):
@@ -430,47 +128,18 @@ class DDIMSampler(object):
             raise NotImplementedError("DDIMSampler(HIP): ddim_use_original_steps=True is not runnable in the reference either "
                                       "(ddim.py:324-327 reads a buffer the model does not have)")
         dev = torch.device("cuda")
+        shape = tuple(shape)
         b = shape[0]
-        ts = self.ddim_timesteps
-        t_start = check_t_start(t_start, timesteps, ts.shape[0])
-        if t_start is not None:
-            ts = ts[:t_start]   # as `decode` cuts it (ddim.py:466-467)
-        if timesteps is not None:
-            # ddim.py:198-206: sample only the first `subset_end` entries of the DDIM sequence (start from a less noisy state)
-            subset_end = int(min(timesteps / ts.shape[0], 1) * ts.shape[0]) - 1
-            ts = ts[:subset_end]
-        total_steps = ts.shape[0]
-        time_range = np.flip(ts).copy()   # own storage, positive strides: from_numpy refuses the flipped view, even of one entry
-        use_cfg = not (unconditional_conditioning is None or unconditional_guidance_scale == 1.0)
+        # RNG contract R: x_T first, then the per-step draws, all from the host generator in the reference's order; the per-step
+        # draws are streamed (see _NoiseFeed).  The table: the schedule's rows total_steps-1 ... 0
+        plan = self.plan_run(cond, shape, x_T, t_start, timesteps,
+                             lambda n, cfg: guidance_table(self.ddim_coef[:n].flip(0), unconditional_guidance_scale, cfg,
+                                                           guidance_rescale),
+                             unconditional_guidance_scale, unconditional_conditioning, guidance_rescale, mask, x0)
+        total_steps, use_cfg, rescale, img, prepared = plan.total_steps, plan.use_cfg, plan.rescale, plan.img, plan.prepared
+        intermediates = {"x_inter": [img], "pred_x0": [img]}
         if total_steps == 0:
-            # `timesteps` <= one DDIM interval: the reference's loop runs zero iterations and returns x_T (ddim.py:198-262)
-            img = (self._drawer(tuple(shape))() if x_T is None else x_T.detach().float().cpu()).to(dev).contiguous()
-            return img, {"x_inter": [img], "pred_x0": [img]}
-
-        # RNG contract R: x_T first, then the per-step draws, all from the host generator in the
-        # reference's order; the per-step draws are streamed (see _NoiseFeed)
-        draw = self._drawer(tuple(shape))
-        # a start latent that already lives on the device (audio-to-audio) stays there
-        img = (draw().to(dev) if x_T is None else x_T.detach().float().to(dev)).contiguous()
-        # device tables in loop order (i = 0 is the noisiest step, index = total_steps - 1)
-        order = [total_steps - i - 1 for i in range(total_steps)]
-        # guidance rescale: the combine and the per-sample rescale run in a launch of their own in front of the step kernel
-        rescale = use_cfg and guidance_rescale > 0.0
-        coef = guidance_table(self.ddim_coef[order], unconditional_guidance_scale, use_cfg, guidance_rescale).to(dev)
-        nrep = 2 if use_cfg else 1
-        t_tab = torch.from_numpy(np.ascontiguousarray(time_range)).float()[:, None].repeat(1, nrep * b).to(dev).contiguous()
-
-        if mask is not None:
-            assert x0 is not None
-            mask_d = mask.float().to(dev).expand(shape).contiguous()
-            x0_d = x0.float().to(dev).contiguous()
-            tr = torch.from_numpy(np.ascontiguousarray(time_range - 0))
-            blend_coef = torch.stack([self.sqrt_alphas_cumprod[tr], self.sqrt_one_minus_alphas_cumprod[tr]],
-                                     1).contiguous().to(dev)  # [S, 2] = {sqrt(abar_t), sqrt(1 - abar_t)}
-
-        cfg_fused = use_cfg and hasattr(self.model, "apply_model_cfg")
-        prepared = self.model.prepare_cfg(cond, unconditional_conditioning) \
-            if cfg_fused and hasattr(self.model, "prepare_cfg") else None
+            return img, intermediates
 
         # The captured step graph, its static input buffers and the batched conditioning live on the UNet
         # module and are reused by the next sampling run of the same geometry (text_to_audio in a loop):
@@ -487,7 +156,7 @@ class DDIMSampler(object):
         key = None
         if can_cache:
             # `rescale`: the launch sequence differs; the VALUES of the scale and phi live in coef_all, copied in below
-            key = (tuple(shape), total_steps, tuple(tuple(c.shape) for c in prepared["ctxs"]),
+            key = (shape, total_steps, tuple(tuple(c.shape) for c in prepared["ctxs"]),
                    None if prepared["y"] is None else tuple(prepared["y"].shape), rescale)
         ent = unet._graph_cache.get(key) if can_cache else None
         if ent is not None and ent.get("kv") is None:
@@ -502,30 +171,20 @@ class DDIMSampler(object):
                 ent["prepared"]["y"].copy_(prepared["y"])
             unet.refresh_context_kv(ent["kv"])  # in place: the captured graph keeps reading these buffers
             ent["x_cur"].copy_(img)
-            ent["coef_all"].copy_(coef)
-            ent["t_tab"].copy_(t_tab)
+            ent["coef_all"].copy_(plan.coef)
+            ent["t_tab"].copy_(plan.t_tab)
         else:
             # static buffers = the graph's inputs
-            ent = {"x_cur": img.clone(), "pred_x0": torch.empty_like(img), "t_cur": t_tab[0].clone(),
-                   "step_idx": torch.zeros(1, device=dev, dtype=torch.int32), "coef_all": coef.clone(), "t_tab": t_tab.clone(),
-                   "noise_all": torch.empty((total_steps,) + tuple(shape), device=dev, dtype=torch.float32),
-                   "prepared": prepared}
+            ent = {"x_cur": img.clone(), "pred_x0": torch.empty_like(img), "t_cur": plan.t_tab[0].clone(),
+                   "step_idx": torch.zeros(1, device=dev, dtype=torch.int32), "coef_all": plan.coef.clone(),
+                   "t_tab": plan.t_tab.clone(),
+                   "noise_all": torch.empty((total_steps,) + shape, device=dev, dtype=torch.float32), "prepared": prepared}
             if rescale:
                 ent["eps_g"] = torch.empty_like(img)   # the rescaled combined model output
 
             def step(e=ent):
                 x_c = e["x_cur"]
-                if use_cfg:
-                    if cfg_fused:
-                        eps = self.model.apply_model_cfg(x_c, e["t_cur"], cond, unconditional_conditioning,
-                                                         prepared=e["prepared"])
-                    else:
-                        tl = e["t_cur"][:b].long()
-                        e_u = self.model.apply_model(x_c, tl, unconditional_conditioning)
-                        e_c = self.model.apply_model(x_c, tl, cond)
-                        eps = torch.stack([e_u, e_c]).contiguous()
-                else:
-                    eps = self.model.apply_model(x_c, e["t_cur"][:b].long(), cond).contiguous()
+                eps = self.model_output(x_c, e["t_cur"], b, cond, unconditional_conditioning, use_cfg, e["prepared"])
                 if rescale:
                     eps = ops.cfg_rescale_indexed(eps, e["eps_g"], e["coef_all"], e["step_idx"])
                 ops.ddim_step_indexed(x_c, eps, e["noise_all"], e["coef_all"], e["step_idx"], e["pred_x0"])
@@ -545,19 +204,17 @@ class DDIMSampler(object):
         # (ADVICE r3 + r4: opt-OUT, not opt-in — a silent interleaving gives a different noise stream with no diagnostic;
         # INTEGRATION.md §5; ALDM_NOISE_THREAD=0 forces the unthreaded feed for every run).
         cb_rng = any(getattr(f, "uses_rng", True) for f in (callback, img_callback) if f is not None)
-        feed = _NoiseFeed(draw, total_steps, tuple(shape), mask is not None, temperature, dev, noise_buf=ent["noise_all"],
+        feed = _NoiseFeed(plan.draw, total_steps, shape, mask is not None, temperature, dev, noise_buf=ent["noise_all"],
                           **({"threaded": False, "chunk": 1} if cb_rng else {}))
         feed.produce_next()
         qn = feed.qnoise
         run_step = ent["run_step"]
-        intermediates = {"x_inter": [img], "pred_x0": [img]}
         try:
-            for i, step_t in enumerate(time_range):
-                index = total_steps - i - 1
+            for i in range(total_steps):
                 opens_chunk = feed.wait(i)  # current stream waits for the upload of step i's noise chunk
                 if mask is not None:
                     # img = q_sample(x0, ts)*mask + (1-mask)*img   (ddim.py:226-231, ddpm.py:430-436)
-                    ops.inpaint_blend(x_cur, x0_d, qn[i], mask_d, blend_coef[i])
+                    ops.inpaint_blend(x_cur, plan.x0_d, qn[i], plan.mask_d, plan.blend_coef[i])
                 run_step()  # eager the first time, then one HIP-graph replay per step
                 if can_cache and ent.get("kv") is None:
                     # after the eager first step: the K/V projections of this run's contexts exist; the cache entry owns
@@ -565,13 +222,7 @@ class DDIMSampler(object):
                     ent["kv"] = unet.collect_context_kv(ent["prepared"]["ctxs"])
                 if opens_chunk and not cb_rng:
                     feed.produce_next()  # (unthreaded mode only) draw + upload the NEXT chunk while the GPU works on this one
-                if callback:
-                    callback(i)
-                if img_callback:
-                    img_callback(pred_x0, i)
-                if index % log_every_t == 0 or index == total_steps - 1:
-                    intermediates["x_inter"].append(x_cur.clone())
-                    intermediates["pred_x0"].append(pred_x0.clone())
+                log_step(i, total_steps, log_every_t, x_cur, pred_x0, intermediates, callback, img_callback)
         finally:
             feed.close()   # the generator is past the run's last draw before anyone else draws from it
         return x_cur.clone(), intermediates
@@ -586,14 +237,7 @@ class DDIMSampler(object):
         guidance_rescale = check_guidance_rescale(guidance_rescale)
         b = x.shape[0]
         use_cfg = not (unconditional_conditioning is None or unconditional_guidance_scale == 1.0)
-        if use_cfg:
-            if hasattr(self.model, "apply_model_cfg"):
-                eps = self.model.apply_model_cfg(x, t.float().repeat(2), c, unconditional_conditioning)
-            else:
-                eps = torch.stack([self.model.apply_model(x, t, unconditional_conditioning),
-                                   self.model.apply_model(x, t, c)]).contiguous()
-        else:
-            eps = self.model.apply_model(x, t, c).contiguous()
+        eps = self.model_output(x, t.float().repeat(2 if use_cfg else 1), b, c, unconditional_conditioning, use_cfg, None)
         coef = guidance_table(self.ddim_coef[index].reshape(1, 5), unconditional_guidance_scale, use_cfg, guidance_rescale)
         if use_cfg and guidance_rescale > 0.0:
             eps = ops.cfg_rescale_indexed(eps, torch.empty_like(eps[0]), coef.to(x.device))

@@ -19,7 +19,7 @@ On MI355X:
     slab, which is also the pred_x0 output;
   * the order of a step is a column of its coefficient row (w = 0: first order, the slab is not read), so EVERY step, step 0
     included, is the same launch sequence on one stream: UNet pass -> dpmpp_step_indexed -> step_advance, run eagerly once,
-    captured into a HIP graph at the second step and replayed after (ddim.GraphStepper).  The graph lives for one sampling run;
+    captured into a HIP graph at the second step and replayed after (sampling.GraphStepper).  The graph lives for one sampling run;
     nothing is read from or written to the UNet's DDIM graph cache;
   * the coefficient table is built in fp64 from the fp32 `alphas_cumprod` buffer and rounded once to fp32
     (dpmpp_2m_coefficients);
@@ -29,14 +29,11 @@ On MI355X:
 """
 from __future__ import annotations
 
-import os
-
 import numpy as np
 import torch
 
 from . import ops
-from .ddim import (GraphStepper, check_guidance_rescale, check_t_start, guidance_table, host_drawer, make_ddim_sampling_parameters,
-                   make_ddim_timesteps)
+from .sampling import GraphStepper, SamplerBase, check_guidance_rescale, check_t_start, guidance_table, log_step
 
 LOWER_ORDER_FINAL_BELOW = 15   # runs shorter than this take their last step at first order
 
@@ -61,37 +58,21 @@ def dpmpp_2m_coefficients(alphas, alphas_prev):
     return np.stack([sigma_t, alpha_t, sigma_p / sigma_t, -alpha_p * np.expm1(-h), w], 1)
 
 
-class DPMSolverSampler(object):
+class DPMSolverSampler(SamplerBase):
+    ORIGINAL_STEPS = "is not supported (the other samplers refuse it too)"
+
     def __init__(self, model, schedule="linear", **kwargs):
-        super().__init__()
-        self.model = model
-        self.ddpm_num_timesteps = model.num_timesteps
-        self.schedule = schedule
-        self.use_graph = os.environ.get("ALDM_NO_GRAPH", "0") != "1"
-        # (global_batch, row_offset) when this process samples one shard of a larger batch (dist.py)
-        self.noise_shard = getattr(model, "noise_shard", None)
+        super().__init__(model, schedule)
         # phi of Lin et al. 2023 (section 3.4), 0: off.  Sampler state, as in PLMSSampler, whose parameter lists this class
         # carries: `sample` sets it on every call from its `guidance_rescale=` keyword (absent: 0), `dpm_sampling` reads it.
         self.guidance_rescale = 0.0
         self.t_start = None   # the same way: `sample` sets it from its `t_start=` keyword (absent: None), `dpm_sampling` reads it
 
-    def register_buffer(self, name, attr):
-        setattr(self, name, attr)
-
     def make_schedule(self, ddim_num_steps, ddim_discretize="uniform", ddim_eta=0.0, verbose=True):
         """DDIM's timestep grid and abar tables at eta = 0 (host side), and the solver's coefficient table for the whole grid."""
         if ddim_eta != 0:
             raise ValueError("ddim_eta must equal 0 for DPM-Solver++(2M): the solver is deterministic")
-        self.ddim_timesteps = make_ddim_timesteps(ddim_discretize, ddim_num_steps, self.ddpm_num_timesteps, verbose)
-        alphas_cumprod = self.model.alphas_cumprod.detach().float().cpu()
-        assert alphas_cumprod.shape[0] == self.ddpm_num_timesteps, "alphas have to be defined for each timestep"
-        self.register_buffer("alphas_cumprod", alphas_cumprod)
-        self.register_buffer("sqrt_alphas_cumprod", torch.sqrt(alphas_cumprod))
-        self.register_buffer("sqrt_one_minus_alphas_cumprod", torch.sqrt(1.0 - alphas_cumprod))
-        sig, a, a_prev = make_ddim_sampling_parameters(alphas_cumprod, self.ddim_timesteps, ddim_eta, verbose)
-        self.register_buffer("ddim_sigmas", sig)
-        self.register_buffer("ddim_alphas", a)
-        self.register_buffer("ddim_alphas_prev", a_prev)
+        super().make_schedule(ddim_num_steps, ddim_discretize, ddim_eta, verbose)
         self.dpm_coef = self._table(len(self.ddim_timesteps))
 
     def _table(self, total_steps):
@@ -123,24 +104,6 @@ class DPMSolverSampler(object):
                                  unconditional_conditioning=unconditional_conditioning)
 
     # ------------------------------------------------------------------------------------------
-    @staticmethod
-    def _refuse(ddim_use_original_steps, quantize_denoised, score_corrector, noise_dropout):
-        if ddim_use_original_steps:
-            raise NotImplementedError("DPMSolverSampler(HIP): ddim_use_original_steps=True is not supported (the other samplers "
-                                      "refuse it too)")
-        if quantize_denoised or score_corrector is not None or noise_dropout != 0.0:
-            raise NotImplementedError("DPMSolverSampler(HIP): option not used by the AudioLDM2 pipeline")
-
-    def _model_output(self, x, t_row, b, cond, uncond, use_cfg, prepared):
-        """The UNet pass of one step: eps [2, b, ...] = [uncond ; cond] under guidance (combined inside the step kernel), else
-        eps [b, ...].  t_row: the step's timestep as floats, one entry per UNet row."""
-        if not use_cfg:
-            return self.model.apply_model(x, t_row[:b].long(), cond).contiguous()
-        if hasattr(self.model, "apply_model_cfg"):
-            return self.model.apply_model_cfg(x, t_row, cond, uncond, prepared=prepared)
-        tl = t_row[:b].long()
-        return torch.stack([self.model.apply_model(x, tl, uncond), self.model.apply_model(x, tl, cond)]).contiguous()
-
     @torch.no_grad()
     def dpm_sampling(self, cond, shape, x_T=None, ddim_use_original_steps=False, callback=None, timesteps=None,
                      quantize_denoised=False, mask=None, x0=None, img_callback=None, log_every_t=100, temperature=1.0,
@@ -152,42 +115,17 @@ class DPMSolverSampler(object):
         dev = torch.device("cuda")
         shape = tuple(shape)
         b = shape[0]
-        ts = self.ddim_timesteps
-        t_start = check_t_start(self.t_start, timesteps, ts.shape[0])
-        if t_start is not None:
-            ts = ts[:t_start]   # exactly the schedule's first t_start entries, indices t_start-1 ... 0, from x_T
-        if timesteps is not None:
-            # as DDIM and PLMS: sample only the first `subset_end` entries of the sequence (start from a less noisy state)
-            subset_end = int(min(timesteps / ts.shape[0], 1) * ts.shape[0]) - 1
-            ts = ts[:subset_end]
-        total_steps = ts.shape[0]
-        time_range = np.flip(ts).copy()   # own storage, positive strides: from_numpy refuses the flipped view, even of one entry
-        use_cfg = not (unconditional_conditioning is None or unconditional_guidance_scale == 1.0)
-        # the host generator: x_T first, then (inpainting only) one q_sample draw per step — nothing else
-        draw = host_drawer(shape, self.noise_shard)
-        # a start latent that already lives on the device (audio-to-audio) stays there
-        img = (draw().to(dev) if x_T is None else x_T.detach().float().to(dev)).contiguous()
+        # the host generator: x_T first, then (inpainting only) one q_sample draw per step — nothing else.  The table: a
+        # sub-range has its own (its own first and last step)
+        plan = self.plan_run(cond, shape, x_T, self.t_start, timesteps,
+                             lambda n, cfg: guidance_table(self.dpm_coef if n == self.dpm_coef.shape[0] else self._table(n),
+                                                           unconditional_guidance_scale, cfg, guidance_rescale),
+                             unconditional_guidance_scale, unconditional_conditioning, guidance_rescale, mask, x0)
+        total_steps, use_cfg, rescale, draw, img = plan.total_steps, plan.use_cfg, plan.rescale, plan.draw, plan.img
         intermediates = {"x_inter": [img], "pred_x0": [img]}
         if total_steps == 0:
-            # `timesteps` <= one interval: the loop runs zero iterations and returns x_T
             return img, intermediates
-
-        # device tables in loop order; a sub-range has its own table (its own first and last step)
-        # guidance rescale: the combine and the per-sample rescale run in a launch of their own in front of the step kernel
-        rescale = use_cfg and guidance_rescale > 0.0
-        coef = guidance_table(self.dpm_coef if total_steps == self.dpm_coef.shape[0] else self._table(total_steps),
-                              unconditional_guidance_scale, use_cfg, guidance_rescale).to(dev)
-        nrep = 2 if use_cfg else 1
-        t_tab = torch.from_numpy(time_range).float()[:, None].repeat(1, nrep * b).to(dev).contiguous()
-        if mask is not None:
-            assert x0 is not None
-            mask_d = mask.float().to(dev).expand(shape).contiguous()
-            x0_d = x0.float().to(dev).contiguous()
-            tr = torch.from_numpy(time_range)
-            blend_coef = torch.stack([self.sqrt_alphas_cumprod[tr], self.sqrt_one_minus_alphas_cumprod[tr]],
-                                     1).contiguous().to(dev)  # [S, 2] = {sqrt(abar_t), sqrt(1 - abar_t)}
-        prepared = self.model.prepare_cfg(cond, unconditional_conditioning) \
-            if use_cfg and hasattr(self.model, "apply_model_cfg") and hasattr(self.model, "prepare_cfg") else None
+        coef, t_tab, prepared = plan.coef, plan.t_tab, plan.prepared
 
         # static buffers = the inputs of the step graph.  pred_x0 is the solver's history slab: step 0 (w = 0) does not read it
         x_cur, pred_x0 = img.clone(), torch.empty_like(img)
@@ -196,29 +134,19 @@ class DPMSolverSampler(object):
         eps_g = torch.empty_like(img) if rescale else None   # the rescaled combined model output
 
         def step():
-            eps = self._model_output(x_cur, t_cur, b, cond, unconditional_conditioning, use_cfg, prepared)
+            eps = self.model_output(x_cur, t_cur, b, cond, unconditional_conditioning, use_cfg, prepared)
             if rescale:
                 eps = ops.cfg_rescale_indexed(eps, eps_g, coef, step_idx)
             ops.dpmpp_step_indexed(x_cur, eps, pred_x0, coef, step_idx)
             ops.step_advance(step_idx, t_tab, t_cur)
         run_step = GraphStepper(step, self.use_graph)   # every step: eager once, captured at the next, replayed after
-        for i, _ in enumerate(time_range):
-            index = total_steps - i - 1
+        for i in range(total_steps):
             if mask is not None:
                 # img = q_sample(x0, ts)*mask + (1-mask)*img, between the replays; its draw comes first
-                ops.inpaint_blend(x_cur, x0_d, draw().to(dev), mask_d, blend_coef[i])
+                ops.inpaint_blend(x_cur, plan.x0_d, draw().to(dev), plan.mask_d, plan.blend_coef[i])
             run_step()
-            if callback:
-                callback(i)
-            if img_callback:
-                img_callback(pred_x0, i)
-            if index % log_every_t == 0 or index == total_steps - 1:
-                intermediates["x_inter"].append(x_cur.clone())
-                intermediates["pred_x0"].append(pred_x0.clone())
+            log_step(i, total_steps, log_every_t, x_cur, pred_x0, intermediates, callback, img_callback)
         out = x_cur.clone()
-        # the stepper, its graph and the step closure form a reference cycle: break it here, where no stream is capturing and
-        # no replay is in flight, instead of leaving the graph and its memory pool to the cyclic collector (ddim.GraphStepper)
-        torch.cuda.synchronize()
-        run_step.fn = None
-        run_step.graph = None
+        torch.cuda.synchronize()   # no replay in flight
+        run_step.release()
         return out, intermediates

@@ -310,7 +310,7 @@ def negative_batch(batch, negative_prompt):
 def _guidance_kwargs(kwargs, unconditional_guidance_scale, batch, ddim_steps):
     """`negative_prompt` and `guidance_rescale` of generate_batch / generate_batch_masked (they travel in **kwargs like `sampler`):
     -> (the negative batch or None, phi), refused before anything is drawn or computed."""
-    from .ddim import check_guidance_rescale
+    from .sampling import check_guidance_rescale
     phi = check_guidance_rescale(kwargs.get("guidance_rescale", 0.0))
     if phi != 0.0 and ddim_steps is None:
         raise ValueError("guidance_rescale needs ddim_steps: the ancestral sampler has no guidance")
@@ -333,6 +333,49 @@ def _tile_cond(c, n_gen):
         else:
             c[k] = torch.cat([c[k]] * n_gen, dim=0)
     return c
+
+
+def _unconditional_half(ld, neg_batch, n_gen, batch_size, unconditional_guidance_scale, unconditional_conditioning=None):
+    """The unconditional half of classifier-free guidance for a job of generate_batch / generate_batch_masked /
+    generate_batch_from_audio: the negative prompt's conditioning (a second conditioner pass, after the positive one), else at a
+    scale != 1.0 each conditioner's `get_unconditional_condition` (ddpm.py:1525-1535), else what the caller passed in."""
+    if neg_batch is not None:
+        return _tile_cond(ld.get_learned_conditioning_dict(neg_batch), n_gen)
+    if unconditional_guidance_scale != 1.0:
+        return {key: ld.cond_stage_models[meta["model_idx"]].get_unconditional_condition(batch_size)
+                for key, meta in ld.cond_stage_model_metadata.items()}
+    return unconditional_conditioning
+
+
+def _sample_log_keywords(sampler, guidance_rescale, t_start=None):
+    """sample_log's optional keywords, each absent at its default: without them the call is the reference's."""
+    kw = {} if sampler is None else {"sampler": sampler}
+    if guidance_rescale != 0.0:
+        kw["guidance_rescale"] = guidance_rescale
+    if t_start is not None:
+        kw["t_start"] = t_start
+    return kw
+
+
+def _waveform_of(ld, samples, batch, text, n_gen, n_prompts, decision_shard=None):
+    """The tail of a job: latent -> mel -> waveform, and with n_gen > 1 candidates per prompt (candidate-major, `n_prompts` rows per
+    candidate) the one whose CLAP audio embedding is closest to the text's (ddpm.py:1554-1568, 1660-1670).  `decision_shard`
+    (prompt-sharded text-to-audio): CLAP consumes the GLOBAL batch's unconditional-probability draws and keeps our rows' decisions."""
+    mel = ld.decode_first_stage_cl(samples)  # [B, T, F, 1]
+    waveform = ld.mel_spectrogram_to_waveform(mel.view(mel.shape[0], mel.shape[1], mel.shape[2]),
+                                              savepath="", bs=None, name=batch.get("fname"), save=False)
+    if n_gen > 1:
+        if decision_shard is not None:
+            ld.clap.decision_shard = decision_shard
+        try:
+            similarity = ld.clap.cos_similarity(torch.FloatTensor(waveform).squeeze(1), text)
+        finally:
+            if decision_shard is not None:
+                ld.clap.decision_shard = None
+        best = [i + torch.argmax(similarity[i::n_prompts]).item() * n_prompts for i in range(n_prompts)]
+        waveform = waveform[best]
+        ld.last_similarity, ld.last_best_index = similarity.detach().cpu(), best
+    return waveform
 
 
 class LatentDiffusion(nn.Module):
@@ -573,7 +616,7 @@ class LatentDiffusion(nn.Module):
         """ddpm.py:1418-1474; `sampler="dpmpp_2m"` (a keyword of **kwargs, no reference counterpart) runs DPMSolverSampler."""
         sampler_name = resolve_sampler(kwargs.pop("sampler", None), use_plms)
         # `guidance_rescale` (phi of Lin et al. 2023, a keyword of **kwargs too) goes to whichever of the three samplers runs
-        from .ddim import check_guidance_rescale
+        from .sampling import check_guidance_rescale
         if check_guidance_rescale(kwargs.get("guidance_rescale", 0.0)) == 0.0:
             kwargs.pop("guidance_rescale", None)   # off: today's call, unchanged
         elif not (use_plms or sampler_name is not None or ddim):
@@ -593,31 +636,26 @@ class LatentDiffusion(nn.Module):
             shape = tuple(kwargs["x_T"].shape[1:])
         else:
             shape = (self.channels, self.latent_t_size, self.latent_f_size)
+        # the sampler classes are looked up on their modules at every call (a reference user, and the tests, rebind them)
         if use_plms:
             # ddpm.py:1449-1461 (mask / x0 / eta travel on; eta != 0 raises in PLMSSampler.make_schedule)
-            from .plms import PLMSSampler
-            samples, _ = PLMSSampler(self).sample(ddim_steps, batch_size, shape, cond, verbose=False,
-                                                  unconditional_guidance_scale=unconditional_guidance_scale, mask=mask,
-                                                  unconditional_conditioning=unconditional_conditioning, **kwargs)
-            return samples, None
-        if sampler_name == "dpmpp_2m":
+            from . import plms
+            sampler = plms.PLMSSampler(self)
+        elif sampler_name == "dpmpp_2m":
             # mask / x0 / eta travel on; eta != 0 raises in DPMSolverSampler.make_schedule, as for PLMS
             if ddim_steps is None:
                 raise ValueError("sampler='dpmpp_2m' needs ddim_steps")
-            from .dpm_solver import DPMSolverSampler
-            samples, _ = DPMSolverSampler(self).sample(ddim_steps, batch_size, shape, cond, verbose=False,
-                                                       unconditional_guidance_scale=unconditional_guidance_scale, mask=mask,
-                                                       unconditional_conditioning=unconditional_conditioning, **kwargs)
-            return samples, None
-        if not ddim:
+            from . import dpm_solver
+            sampler = dpm_solver.DPMSolverSampler(self)
+        elif ddim:
+            sampler = DDIMSampler(self, device=self.device)
+        else:
             kwargs.pop("eta", None)  # the ancestral sampler has no eta (the reference would raise here)
             samples = self.sample(cond=cond, batch_size=batch_size, mask=mask, **kwargs)
             return samples, None
-        sampler = DDIMSampler(self, device=self.device)
         samples, _ = sampler.sample(ddim_steps, batch_size, shape, cond, verbose=False,
                                     unconditional_guidance_scale=unconditional_guidance_scale,
-                                    unconditional_conditioning=unconditional_conditioning, mask=mask,
-                                    **kwargs)
+                                    unconditional_conditioning=unconditional_conditioning, mask=mask, **kwargs)
         return samples, None
 
     @torch.no_grad()
@@ -644,7 +682,7 @@ class LatentDiffusion(nn.Module):
         (:364-373) at clip_denoised=False (LatentDiffusion sets it, ddpm.py:677).  One UNet pass + one
         fused update kernel per timestep, HIP-graph replayed; noise from the host generator in the
         reference's order: x_T, then per step [p_sample noise, q_sample noise when inpainting]."""
-        from .ddim import GraphStepper, _NoiseFeed
+        from .sampling import GraphStepper, _NoiseFeed, host_drawer
         if quantize_denoised:
             raise NotImplementedError("quantize_denoised is a VQ option; AudioLDM2 uses a KL first stage")
         dev = self.device
@@ -656,7 +694,6 @@ class LatentDiffusion(nn.Module):
             timesteps = self.num_timesteps
         if start_T is not None:
             timesteps = min(timesteps, start_T)
-        from .ddim import host_drawer
         draw = host_drawer(shape, getattr(self, "noise_shard", None))   # sharded runs draw the global batch, keep our rows
         img_h = draw() if x_T is None else x_T.detach().float().cpu()
         x_cur = img_h.to(dev).contiguous()
@@ -832,14 +869,8 @@ class LatentDiffusion(nn.Module):
         batch_size = B0 * n_gen
         c = _tile_cond(c, n_gen)
         text = list(batch["text"]) * n_gen
-        if neg_batch is not None:
-            # the negative prompt's conditioning is the unconditional half: a second conditioner pass, after the positive one
-            unconditional_conditioning = _tile_cond(self.get_learned_conditioning_dict(neg_batch), n_gen)
-        elif unconditional_guidance_scale != 1.0:
-            unconditional_conditioning = {}
-            for key, meta in self.cond_stage_model_metadata.items():
-                unconditional_conditioning[key] = self.cond_stage_models[
-                    meta["model_idx"]].get_unconditional_condition(batch_size)
+        unconditional_conditioning = _unconditional_half(self, neg_batch, n_gen, batch_size, unconditional_guidance_scale,
+                                                         unconditional_conditioning)
         shard = kwargs.get("shard", None)  # (rank, world): sample only this process's contiguous slice of the PROMPTS
         self.noise_shard = None
         Bp = B0                                  # prompts sampled by this process
@@ -869,28 +900,11 @@ class LatentDiffusion(nn.Module):
                                          ddim_steps=ddim_steps, eta=ddim_eta,
                                          unconditional_guidance_scale=unconditional_guidance_scale,
                                          unconditional_conditioning=unconditional_conditioning,
-                                         use_plms=use_plms, **({} if sampler is None else {"sampler": sampler}),
-                                         **({} if guidance_rescale == 0.0 else {"guidance_rescale": guidance_rescale}))
+                                         use_plms=use_plms, **_sample_log_keywords(sampler, guidance_rescale))
         finally:
             self.noise_shard = None
-        mel = self.decode_first_stage_cl(samples)  # [B, T, F, 1]
-        waveform = self.mel_spectrogram_to_waveform(mel.view(mel.shape[0], mel.shape[1], mel.shape[2]),
-                                                    savepath="", bs=None, name=batch.get("fname"), save=False)
-        if n_gen > 1:
-            # ddpm.py:1554-1568: keep, per prompt, the candidate whose CLAP audio embedding is closest to the text's
-            if shard is not None:   # consume the GLOBAL batch's unconditional-probability draws, keep our rows' decisions
-                self.clap.decision_shard = (B0 * n_gen, rows.tolist())
-            try:
-                similarity = self.clap.cos_similarity(torch.FloatTensor(waveform).squeeze(1), text)
-            finally:
-                self.clap.decision_shard = None
-            best = []
-            for i in range(Bp):
-                cand = similarity[i::Bp]
-                best.append(i + torch.argmax(cand).item() * Bp)
-            waveform = waveform[best]
-            self.last_similarity, self.last_best_index = similarity.detach().cpu(), best
-        return waveform
+        return _waveform_of(self, samples, batch, text, n_gen, Bp,
+                            decision_shard=None if shard is None else (B0 * n_gen, rows.tolist()))
 
 
     @torch.no_grad()
@@ -922,28 +936,13 @@ class LatentDiffusion(nn.Module):
         mask = mask[:, None, ...]
         c = _tile_cond(c, n_gen)
         text = list(batch["text"]) * n_gen
-        if neg_batch is not None:
-            # the negative prompt's conditioning is the unconditional half: a second conditioner pass, after the positive one
-            unconditional_conditioning = _tile_cond(self.get_learned_conditioning_dict(neg_batch), n_gen)
-        elif unconditional_guidance_scale != 1.0:
-            unconditional_conditioning = {}
-            for key, meta in self.cond_stage_model_metadata.items():
-                unconditional_conditioning[key] = self.cond_stage_models[
-                    meta["model_idx"]].get_unconditional_condition(batch_size)
+        unconditional_conditioning = _unconditional_half(self, neg_batch, n_gen, batch_size, unconditional_guidance_scale,
+                                                         unconditional_conditioning)
         samples, _ = self.sample_log(cond=c, batch_size=batch_size, x_T=x_T, ddim=use_ddim, ddim_steps=ddim_steps,
                                      eta=ddim_eta, unconditional_guidance_scale=unconditional_guidance_scale,
                                      unconditional_conditioning=unconditional_conditioning, use_plms=use_plms,
-                                     mask=mask, x0=torch.cat([z] * n_gen), **({} if sampler is None else {"sampler": sampler}),
-                                     **({} if guidance_rescale == 0.0 else {"guidance_rescale": guidance_rescale}))
-        mel = self.decode_first_stage_cl(samples)
-        waveform = self.mel_spectrogram_to_waveform(mel.view(mel.shape[0], mel.shape[1], mel.shape[2]),
-                                                    savepath="", bs=None, name=batch.get("fname"), save=False)
-        if n_gen > 1:
-            similarity = self.clap.cos_similarity(torch.FloatTensor(waveform).squeeze(1), text)   # ddpm.py:1660-1670
-            best = [i + torch.argmax(similarity[i::B0]).item() * B0 for i in range(B0)]
-            waveform = waveform[best]
-            self.last_similarity, self.last_best_index = similarity.detach().cpu(), best
-        return waveform
+                                     mask=mask, x0=torch.cat([z] * n_gen), **_sample_log_keywords(sampler, guidance_rescale))
+        return _waveform_of(self, samples, batch, text, n_gen, B0)
 
 
     @torch.no_grad()
@@ -980,15 +979,7 @@ class LatentDiffusion(nn.Module):
         batch_size = B0 * n_gen
         c = _tile_cond(c, n_gen)
         text = list(batch["text"]) * n_gen
-        unconditional_conditioning = None
-        if neg_batch is not None:
-            # the negative prompt's conditioning is the unconditional half: a second conditioner pass, after the positive one
-            unconditional_conditioning = _tile_cond(self.get_learned_conditioning_dict(neg_batch), n_gen)
-        elif unconditional_guidance_scale != 1.0:
-            unconditional_conditioning = {}
-            for key, meta in self.cond_stage_model_metadata.items():
-                unconditional_conditioning[key] = self.cond_stage_models[
-                    meta["model_idx"]].get_unconditional_condition(batch_size)
+        unconditional_conditioning = _unconditional_half(self, neg_batch, n_gen, batch_size, unconditional_guidance_scale)
         n_enc = torch.randn((batch_size, C, h, w))                 # the forward-diffusion noise, in the place of the x_T draw
         # {scale_factor, sqrt(abar), sqrt(1 - abar)} on the device; a scale_factor buffer is read where it lives (no host round trip)
         coef = torch.tensor([1.0 if torch.is_tensor(self.scale_factor) else float(self.scale_factor), sa, so],
@@ -996,20 +987,11 @@ class LatentDiffusion(nn.Module):
         if torch.is_tensor(self.scale_factor):
             coef[0:1].copy_(self.scale_factor.detach().reshape(1))
         _, x_t = ops.posterior_qsample(moments, n_post.to(self.device), n_enc.to(self.device), coef)
-        samples, _ = self.sample_log(cond=c, batch_size=batch_size, x_T=x_t, t_start=t_enc, ddim=True, ddim_steps=ddim_steps,
-                                     eta=ddim_eta, unconditional_guidance_scale=unconditional_guidance_scale,
+        samples, _ = self.sample_log(cond=c, batch_size=batch_size, x_T=x_t, ddim=True, ddim_steps=ddim_steps, eta=ddim_eta,
+                                     unconditional_guidance_scale=unconditional_guidance_scale,
                                      unconditional_conditioning=unconditional_conditioning, use_plms=use_plms,
-                                     **({} if sampler is None else {"sampler": sampler}),
-                                     **({} if guidance_rescale == 0.0 else {"guidance_rescale": guidance_rescale}))
-        mel = self.decode_first_stage_cl(samples)
-        waveform = self.mel_spectrogram_to_waveform(mel.view(mel.shape[0], mel.shape[1], mel.shape[2]),
-                                                    savepath="", bs=None, name=batch.get("fname"), save=False)
-        if n_gen > 1:
-            similarity = self.clap.cos_similarity(torch.FloatTensor(waveform).squeeze(1), text)   # ddpm.py:1660-1670
-            best = [i + torch.argmax(similarity[i::B0]).item() * B0 for i in range(B0)]
-            waveform = waveform[best]
-            self.last_similarity, self.last_best_index = similarity.detach().cpu(), best
-        return waveform
+                                     **_sample_log_keywords(sampler, guidance_rescale, t_enc))
+        return _waveform_of(self, samples, batch, text, n_gen, B0)
 
 
 # ------------------------------------------------------------------------------------------------

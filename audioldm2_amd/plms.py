@@ -9,12 +9,15 @@ On MI355X:
   * guidance combine + multistep combine + x0 prediction + x_{t-1} update + the history update are one kernel per step
     (ops.plms_step_indexed; step 0: ops.plms_first_step, twice);
   * the history is a ring of three slabs whose slots follow the device-side step counter, so steps >= 1 are ONE launch sequence:
-    UNet pass -> plms_step_indexed -> step_advance, captured once into a HIP graph on one stream and replayed (ddim.GraphStepper);
+    UNet pass -> plms_step_indexed -> step_advance, captured once into a HIP graph on one stream and replayed (sampling.GraphStepper);
     step 0 runs eagerly.  The graph lives for one sampling run: nothing is read from or written to the UNet's DDIM graph cache;
   * RNG contract: the reference's `get_x_prev_and_pred_x0` draws `noise_like(x.shape)` every time it runs although
     sigma = 0 multiplies the result away (plms.py:334) — two draws in step 0, one in every later step, after the q_sample draw of an
     inpainting step and after x_T.  They are made on the host generator, in that order, on the launching thread, and discarded: the
     next consumer of the generator sees the state the reference leaves.
+
+The schedule, the run plan and the UNet pass come from sampling.SamplerBase, shared with DDIMSampler and DPMSolverSampler; this module
+keeps what is PLMS's own: the eager step 0, the ring, the discarded draws.
 
 Stated deviations: with guidance the reference concatenates the two conditionings with `torch.cat` (plms.py:290),
 which raises for AudioLDM2's dict conditioning; here guidance runs as in DDIMSampler — one pass over [uncond ; cond], e_u + s (e_c -
@@ -22,59 +25,35 @@ e_u).  `make_schedule` raises ValueError for eta != 0 where the reference as shi
 """
 from __future__ import annotations
 
-import os
-
 import numpy as np
 import torch
 
 from . import ops
-from .ddim import (GraphStepper, check_guidance_rescale, check_t_start, guidance_table, host_drawer, make_ddim_sampling_parameters,
-                   make_ddim_timesteps)
+from .sampling import GraphStepper, SamplerBase, check_guidance_rescale, check_t_start, ddim_step_rows, guidance_table, log_step
 
 
-class PLMSSampler(object):
+class PLMSSampler(SamplerBase):
+    # p_sample_plms reads `self.model.ddim_sigmas_for_original_num_steps` there (plms.py:313-317), a buffer make_schedule registered on
+    # the SAMPLER (plms.py:87-89): with LatentDiffusion as the model this path raises AttributeError in the reference itself, so
+    # there is no behaviour to reproduce
+    ORIGINAL_STEPS = "is not runnable in the reference either (plms.py:313-317 reads a buffer the model does not have)"
+
     def __init__(self, model, schedule="linear", **kwargs):
-        super().__init__()
-        self.model = model
-        self.ddpm_num_timesteps = model.num_timesteps
-        self.schedule = schedule
-        self.use_graph = os.environ.get("ALDM_NO_GRAPH", "0") != "1"
-        # (global_batch, row_offset) when this process samples one shard of a larger batch (dist.py)
-        self.noise_shard = getattr(model, "noise_shard", None)
+        super().__init__(model, schedule)
         self.t_start = None   # sampler state like guidance_rescale: `sample` sets it on every call, `plms_sampling` reads it
         # phi of Lin et al. 2023 (section 3.4), 0: off.  Sampler state like the schedule, not a parameter: `plms_sampling` and
         # `p_sample_plms` keep the reference class's signatures, which have no **kwargs to take it.  `sample` sets it on every
         # call from its `guidance_rescale=` keyword (absent: 0); a caller of the two other methods sets the attribute.
         self.guidance_rescale = 0.0
 
-    def register_buffer(self, name, attr):
-        setattr(self, name, attr)
-
     def make_schedule(self, ddim_num_steps, ddim_discretize="uniform", ddim_eta=0.0, verbose=True):
         """plms.py:27-89 (host side, float tables only): DDIM's schedule at eta = 0."""
         if ddim_eta != 0:
             raise ValueError("ddim_eta must equal 0 for PLMS")
-        self.ddim_timesteps = make_ddim_timesteps(ddim_discretize, ddim_num_steps, self.ddpm_num_timesteps, verbose)
-        alphas_cumprod = self.model.alphas_cumprod.detach().float().cpu()
-        assert alphas_cumprod.shape[0] == self.ddpm_num_timesteps, "alphas have to be defined for each timestep"
-        self.register_buffer("alphas_cumprod", alphas_cumprod)
-        self.register_buffer("sqrt_alphas_cumprod", torch.sqrt(alphas_cumprod))
-        self.register_buffer("sqrt_one_minus_alphas_cumprod", torch.sqrt(1.0 - alphas_cumprod))
-        sig, a, a_prev = make_ddim_sampling_parameters(alphas_cumprod, self.ddim_timesteps, ddim_eta, verbose)
-        self.register_buffer("ddim_sigmas", sig)
-        self.register_buffer("ddim_alphas", a)
-        self.register_buffer("ddim_alphas_prev", a_prev)
-        self.register_buffer("ddim_sqrt_one_minus_alphas", np.sqrt(1.0 - a.numpy()))
-        # per-index coefficient rows with the reference's roundings (plms.py:319-338): a_t, a_prev, sigma_t, sqrt(1-a_t)
-        # become fp32 via torch.full; the other square roots are fp32 tensor ops.  Row layout of ops.ddim_step.
-        rows = []
-        for i in range(len(self.ddim_timesteps)):
-            a_t = torch.full((1,), float(a[i]))
-            ap = torch.full((1,), float(a_prev[i]))
-            sg = torch.full((1,), float(sig[i]))
-            som = torch.full((1,), float(self.ddim_sqrt_one_minus_alphas[i]))
-            rows.append(torch.cat([som, a_t.sqrt(), (1.0 - ap - sg ** 2).sqrt(), ap.sqrt(), sg]))
-        self.plms_coef = torch.stack(rows)  # [S, 5] fp32 (host)
+        super().make_schedule(ddim_num_steps, ddim_discretize, ddim_eta, verbose)
+        self.register_buffer("ddim_sqrt_one_minus_alphas", np.sqrt(1.0 - self.ddim_alphas.numpy()))
+        self.plms_coef = ddim_step_rows(self.ddim_sigmas, self.ddim_alphas, self.ddim_alphas_prev,
+                                        self.ddim_sqrt_one_minus_alphas)  # [S, 5] fp32 (host)
 
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None,
@@ -98,27 +77,6 @@ class PLMSSampler(object):
                                   unconditional_conditioning=unconditional_conditioning)
 
     # ------------------------------------------------------------------------------------------
-    @staticmethod
-    def _refuse(ddim_use_original_steps, quantize_denoised, score_corrector, noise_dropout):
-        if ddim_use_original_steps:
-            # p_sample_plms reads `self.model.ddim_sigmas_for_original_num_steps` here (plms.py:313-317), a buffer make_schedule
-            # registered on the SAMPLER (plms.py:87-89): with LatentDiffusion as the model this path raises AttributeError in the
-            # reference itself, so there is no behaviour to reproduce
-            raise NotImplementedError("PLMSSampler(HIP): ddim_use_original_steps=True is not runnable in the reference either "
-                                      "(plms.py:313-317 reads a buffer the model does not have)")
-        if quantize_denoised or score_corrector is not None or noise_dropout != 0.0:
-            raise NotImplementedError("PLMSSampler(HIP): option not used by the AudioLDM2 pipeline")
-
-    def _model_output(self, x, t_row, b, cond, uncond, use_cfg, prepared):
-        """The UNet pass of one step: eps [2, b, ...] = [uncond ; cond] under guidance (combined inside the step kernel), else
-        eps [b, ...].  t_row: the step's timestep as floats, one entry per UNet row."""
-        if not use_cfg:
-            return self.model.apply_model(x, t_row[:b].long(), cond).contiguous()
-        if hasattr(self.model, "apply_model_cfg"):
-            return self.model.apply_model_cfg(x, t_row, cond, uncond, prepared=prepared)
-        tl = t_row[:b].long()
-        return torch.stack([self.model.apply_model(x, tl, uncond), self.model.apply_model(x, tl, cond)]).contiguous()
-
     @torch.no_grad()
     def plms_sampling(self, cond, shape, x_T=None, ddim_use_original_steps=False, callback=None, timesteps=None,
                       quantize_denoised=False, mask=None, x0=None, img_callback=None, log_every_t=100, temperature=1.0,
@@ -130,43 +88,17 @@ class PLMSSampler(object):
         dev = torch.device("cuda")
         shape = tuple(shape)
         b = shape[0]
-        ts = self.ddim_timesteps
-        t_start = check_t_start(self.t_start, timesteps, ts.shape[0])
-        if t_start is not None:
-            ts = ts[:t_start]   # exactly the schedule's first t_start entries, indices t_start-1 ... 0, from x_T
-        if timesteps is not None:
-            # plms.py:190-198: sample only the first `subset_end` entries of the sequence (start from a less noisy state)
-            subset_end = int(min(timesteps / ts.shape[0], 1) * ts.shape[0]) - 1
-            ts = ts[:subset_end]
-        total_steps = ts.shape[0]
-        time_range = np.flip(ts).copy()   # own storage, positive strides: from_numpy refuses the flipped view, even of one entry
-        use_cfg = not (unconditional_conditioning is None or unconditional_guidance_scale == 1.0)
-        # RNG contract R: x_T first, then the per-step draws, all from the host generator on this thread in the reference's order
-        draw = host_drawer(shape, self.noise_shard)
-        # a start latent that already lives on the device (audio-to-audio) stays there
-        img = (draw().to(dev) if x_T is None else x_T.detach().float().to(dev)).contiguous()
+        # RNG contract R: x_T first, then the per-step draws, all from the host generator on this thread in the reference's order.
+        # The table: the schedule's rows total_steps-1 ... 0; with guidance rescale the history ring holds the rescaled e_t
+        plan = self.plan_run(cond, shape, x_T, self.t_start, timesteps,
+                             lambda n, cfg: guidance_table(self.plms_coef[:n].flip(0), unconditional_guidance_scale, cfg,
+                                                           guidance_rescale),
+                             unconditional_guidance_scale, unconditional_conditioning, guidance_rescale, mask, x0)
+        total_steps, use_cfg, rescale, draw, img = plan.total_steps, plan.use_cfg, plan.rescale, plan.draw, plan.img
         intermediates = {"x_inter": [img], "pred_x0": [img]}
         if total_steps == 0:
-            # `timesteps` <= one interval: the reference's loop runs zero iterations and returns x_T
             return img, intermediates
-
-        # device tables in loop order (i = 0 is the noisiest step, index = total_steps - 1)
-        order = [total_steps - i - 1 for i in range(total_steps)]
-        # guidance rescale: the combine and the per-sample rescale run in a launch of their own in front of the step kernels,
-        # so the history ring holds the rescaled e_t
-        rescale = use_cfg and guidance_rescale > 0.0
-        coef = guidance_table(self.plms_coef[order], unconditional_guidance_scale, use_cfg, guidance_rescale).to(dev)
-        nrep = 2 if use_cfg else 1
-        t_tab = torch.from_numpy(time_range).float()[:, None].repeat(1, nrep * b).to(dev).contiguous()
-        if mask is not None:
-            assert x0 is not None
-            mask_d = mask.float().to(dev).expand(shape).contiguous()
-            x0_d = x0.float().to(dev).contiguous()
-            tr = torch.from_numpy(time_range)
-            blend_coef = torch.stack([self.sqrt_alphas_cumprod[tr], self.sqrt_one_minus_alphas_cumprod[tr]],
-                                     1).contiguous().to(dev)  # [S, 2] = {sqrt(abar_t), sqrt(1 - abar_t)}
-        prepared = self.model.prepare_cfg(cond, unconditional_conditioning) \
-            if use_cfg and hasattr(self.model, "apply_model_cfg") and hasattr(self.model, "prepare_cfg") else None
+        coef, t_tab, prepared = plan.coef, plan.t_tab, plan.prepared
 
         # static buffers = the inputs of the step graph
         x_cur, pred_x0 = img.clone(), torch.empty_like(img)
@@ -175,50 +107,40 @@ class PLMSSampler(object):
         t_cur = t_tab[0].clone()
         eps_g = torch.empty_like(img) if rescale else None   # the rescaled combined model output of the replayed step
 
-        def model_output(x, t_row, out=None, idx=None):
+        def guided_eps(x, t_row, out=None, idx=None):
             """eps [2, b, ...] for the step kernel to combine, or with rescale the combined and rescaled [b, ...] (row: the
             counter's, or row 0 — the step's row in the eager calls of step 0)"""
-            eps = self._model_output(x, t_row, b, cond, unconditional_conditioning, use_cfg, prepared)
+            eps = self.model_output(x, t_row, b, cond, unconditional_conditioning, use_cfg, prepared)
             if not rescale:
                 return eps
             return ops.cfg_rescale_indexed(eps, torch.empty_like(img) if out is None else out, coef, idx)
 
         def step():
-            eps = model_output(x_cur, t_cur, eps_g, step_idx)
+            eps = guided_eps(x_cur, t_cur, eps_g, step_idx)
             ops.plms_step_indexed(x_cur, eps, hist, coef, step_idx, pred_x0)
             ops.step_advance(step_idx, t_tab, t_cur)
         run_step = GraphStepper(step, self.use_graph)   # steps >= 1: eager once, captured at the next, replayed after
-        for i, _ in enumerate(time_range):
-            index = total_steps - i - 1
+        for i in range(total_steps):
             if mask is not None:
                 # img = q_sample(x0, ts)*mask + (1-mask)*img   (plms.py:222-227, ddpm.py:430-436); its draw comes first
-                ops.inpaint_blend(x_cur, x0_d, draw().to(dev), mask_d, blend_coef[i])
+                ops.inpaint_blend(x_cur, plan.x0_d, draw().to(dev), plan.mask_d, plan.blend_coef[i])
             if i == 0:
                 # pseudo improved Euler (plms.py:341-345): provisional x_prev from e_t, a second pass at (x_prev, t_next)
-                e_t = model_output(x_cur, t_cur)
+                e_t = guided_eps(x_cur, t_cur)
                 x_tmp, _ = ops.plms_first_step(x_cur, e_t, None, coef[0])
                 draw()                                                   # the noise_like of the provisional update
                 t_next = t_tab[min(1, total_steps - 1)]
-                e_next = model_output(x_tmp, t_next)
+                e_next = guided_eps(x_tmp, t_next)
                 ops.plms_first_step(x_cur, e_t, e_next, coef[0], x_out=x_cur, pred_x0=pred_x0, hist=hist)
                 ops.step_advance(step_idx, t_tab, t_cur)
                 del e_t, e_next, x_tmp
             else:
                 run_step()
             draw()   # the step's noise_like (plms.py:334): consumed after the launch, while the GPU works
-            if callback:
-                callback(i)
-            if img_callback:
-                img_callback(pred_x0, i)
-            if index % log_every_t == 0 or index == total_steps - 1:
-                intermediates["x_inter"].append(x_cur.clone())
-                intermediates["pred_x0"].append(pred_x0.clone())
+            log_step(i, total_steps, log_every_t, x_cur, pred_x0, intermediates, callback, img_callback)
         out = x_cur.clone()
-        # the stepper, its graph and the step closure form a reference cycle: break it here, where no stream is capturing and
-        # no replay is in flight, instead of leaving the graph and its memory pool to the cyclic collector (ddim.GraphStepper)
-        torch.cuda.synchronize()
-        run_step.fn = None
-        run_step.graph = None
+        torch.cuda.synchronize()   # no replay in flight
+        run_step.release()
         return out, intermediates
 
     @torch.no_grad()
@@ -241,17 +163,17 @@ class PLMSSampler(object):
         def noise_like():
             torch.randn((1, *x.shape[1:])) if repeat_noise else torch.randn(x.shape)
 
-        def model_output(xx, tt):
-            eps = self._model_output(xx, tt.float().repeat(nrep), b, c, unconditional_conditioning, use_cfg, None)
+        def guided_eps(xx, tt):
+            eps = self.model_output(xx, tt.float().repeat(nrep), b, c, unconditional_conditioning, use_cfg, None)
             return ops.cfg_rescale_indexed(eps, torch.empty_like(x), coef) if rescale else eps
-        e_t = model_output(x, t)
+        e_t = guided_eps(x, t)
         hist = torch.zeros((3,) + tuple(x.shape), device=x.device, dtype=torch.float32)
         old_eps = list(old_eps or [])[-3:]
         k = len(old_eps)
         if k == 0:
             x_tmp, _ = ops.plms_first_step(x, e_t, None, coef[0])
             noise_like()
-            e_next = model_output(x_tmp, t_next)
+            e_next = guided_eps(x_tmp, t_next)
             x_prev, pred_x0 = ops.plms_first_step(x, e_t, e_next, coef[0], hist=hist)
         else:
             # the ring as the sampling loop would hold it at step k: the j-th newest entry in slot (k - j) % 3

@@ -1,0 +1,434 @@
+"""What the three samplers share (ddim.DDIMSampler, plms.PLMSSampler, dpm_solver.DPMSolverSampler): the host side of a sampling
+run that is the same whichever update rule runs.
+
+  * SamplerBase: the constructor, DDIM's timestep grid and abar tables (`make_schedule`), the run plan (`plan_run`: the cut of the
+    schedule, the start latent, the device tables, the inpainting buffers, the batched guidance conditioning) and the UNet pass of
+    one step (`model_output`);
+  * ddim_step_rows: the [S, 5] coefficient rows of DDIM's update with the reference's roundings (DDIM and PLMS), guidance_table:
+    a sampler's [S, 8] table from its rows;
+  * GraphStepper / drop_graph_entries: a fixed launch sequence run eagerly once, captured into a HIP graph, replayed;
+  * host_drawer / _NoiseFeed: the host generator's draws in the reference's order (RNG contract);
+  * check_guidance_rescale / check_t_start: the two per-run options every sampler takes; log_step: the tail of every step.
+
+What differs between the samplers stays in their modules: DDIM's graph cache on the UNet and its threaded noise feed, PLMS's eager
+Euler step 0 and its discarded `noise_like` draws, DPM-Solver++'s table per sub-range.  ddim.py re-exports every name that lived
+there before this module existed.
+"""
+from __future__ import annotations
+
+import gc
+import os
+from types import SimpleNamespace
+
+import numpy as np
+import torch
+
+
+def make_ddim_timesteps(ddim_discr_method, num_ddim_timesteps, num_ddpm_timesteps, verbose=True):
+    """util.py:55-75"""
+    if ddim_discr_method == "uniform":
+        c = num_ddpm_timesteps // num_ddim_timesteps
+        ddim_timesteps = np.asarray(list(range(0, num_ddpm_timesteps, c)))
+    elif ddim_discr_method == "quad":
+        ddim_timesteps = ((np.linspace(0, np.sqrt(num_ddpm_timesteps * 0.8), num_ddim_timesteps)) ** 2).astype(int)
+    else:
+        raise NotImplementedError(f'There is no ddim discretization method called "{ddim_discr_method}"')
+    return ddim_timesteps + 1
+
+
+def make_ddim_sampling_parameters(alphacums, ddim_timesteps, eta, verbose=True):
+    """util.py:78-95 — keeps the reference's mixed float32-tensor / float64-ndarray arithmetic:
+    (1 - alphas) is a float32 tensor op, the rest float64."""
+    alphas = alphacums[ddim_timesteps]
+    alphas_prev = np.asarray([alphacums[0]] + alphacums[ddim_timesteps[:-1]].tolist())
+    sigmas = eta * np.sqrt((1 - alphas_prev) / (1 - alphas) * (1 - alphas / alphas_prev))
+    return torch.as_tensor(np.asarray(sigmas, dtype=np.float64)), alphas, alphas_prev
+
+
+class GraphStepper:
+    """Runs a fixed launch sequence repeatedly: eagerly the first time (packs weights, warms the
+    allocator, grows the split-K workspace), captured into a HIP graph the second time, replayed after.
+    The callable must read its per-step inputs from static device buffers."""
+
+    def __init__(self, fn, use_graph=True):
+        self.fn, self.use_graph, self.calls, self.graph = fn, use_graph, 0, None
+
+    def __call__(self):
+        if self.use_graph and self.calls >= 1:
+            if self.graph is None:
+                g = torch.cuda.CUDAGraph()
+                torch.cuda.synchronize()
+                # No cyclic garbage collection while the stream is capturing: a collection that happens to run inside the
+                # capture can finalise objects of EARLIER jobs (an evicted step graph, a noise feed's side stream and pinned
+                # buffers) whose destructors call HIP functions that are illegal during capture — the C++ destructor then
+                # throws and the process aborts ("Fatal Python error: Aborted ... Garbage-collecting" a few tests into a
+                # long session, at a different place every time).  Collect first, then hold the collector off.
+                gc.collect()
+                gc_was_on = gc.isenabled()
+                gc.disable()
+                try:
+                    # thread_local: other threads (e.g. the RCCL watchdog of a multi-GPU run) may keep
+                    # calling HIP while this thread captures
+                    with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                        self.fn()
+                    self.graph = g
+                except RuntimeError as e:  # capture refused: keep sampling eagerly, say so once
+                    import sys
+                    print(f"[audioldm2_amd] HIP graph capture failed ({e}); continuing without a graph",
+                          file=sys.stderr, flush=True)
+                    self.use_graph = False
+                    torch.cuda.synchronize()
+                    if gc_was_on:
+                        gc.enable()
+                    self.fn()
+                    self.calls += 1
+                    return
+                finally:
+                    if gc_was_on:
+                        gc.enable()
+            self.graph.replay()
+        else:
+            self.fn()
+        self.calls += 1
+
+    def release(self):
+        """Break the reference cycle stepper -> step closure -> stepper, so the graph, its private memory pool and its static
+        buffers go by reference counting NOW and not with a later cyclic collection, which may run in the middle of the next
+        capture (see __call__).  Call it where no stream is capturing and no replay is in flight."""
+        self.fn = None
+        self.graph = None
+
+
+def drop_graph_entries(cache: dict) -> None:
+    """Evict cached step graphs NOW, by reference counting: an entry is a reference cycle (entry -> stepper -> step closure ->
+    entry), so simply forgetting it leaves the HIP graph to the cyclic collector (see GraphStepper.release).  Breaking the cycle
+    here frees it at a point where no stream is capturing."""
+    for ent in list(cache.values()):
+        rs = ent.get("run_step")
+        if rs is not None:
+            rs.release()
+        ent.clear()
+    cache.clear()
+
+
+class _NoiseFeed:
+    """Streams the per-step host noise to the GPU in chunks.  A DRAWER THREAD consumes the CPU generator (the reference's RNG
+    stream, strictly in its order: only this thread draws while a sampling run is in flight) into pinned staging rows and
+    issues the PCIe uploads on a side stream, running up to `len(pin)` chunks ahead of the GPU; the launching thread only
+    makes its stream wait for a chunk's upload event (`wait(i)`).  Round 2 drew on the launching thread between graph replays:
+    with prompt sharding every rank draws the GLOBAL batch (7 ms per step at 8 ranks x 8 prompts against a 16 ms GPU step,
+    profiles/r02_host_noise_cost.txt) — one kernel speed-up away from bounding the job.  `torch.randn` releases the GIL.
+    Device buffers hold all steps (`noise_buf` / `qnoise_buf`: write into these — the static inputs of a cached step graph —
+    instead of allocating); `close()` joins the thread: after it the generator is where the reference leaves it."""
+
+    def __init__(self, draw, steps, shape, with_mask, temperature, dev, chunk=8, mask_first=True, noise_buf=None,
+                 qnoise_buf=None, threaded=None):
+        import threading
+        self.draw, self.steps, self.with_mask, self.temperature = draw, steps, with_mask, temperature
+        self.mask_first = mask_first  # DDIM draws the q_sample noise before the step noise, DDPM after
+        # chunk boundaries: the first chunk is ONE step so the GPU starts right away, then `chunk` steps
+        self.bounds = [0, min(1, steps)]
+        while self.bounds[-1] < steps:
+            self.bounds.append(min(steps, self.bounds[-1] + chunk))
+        self.chunk = chunk
+        self.noise = noise_buf if noise_buf is not None else torch.empty((steps,) + tuple(shape), device=dev,
+                                                                         dtype=torch.float32)
+        assert self.noise.shape == (steps,) + tuple(shape)
+        self.qnoise = (qnoise_buf if qnoise_buf is not None else torch.empty_like(self.noise)) if with_mask else None
+        nbuf = 3
+        self.pin = [torch.empty((chunk,) + tuple(shape)).pin_memory() for _ in range(nbuf)]
+        self.qpin = [torch.empty((chunk,) + tuple(shape)).pin_memory() for _ in range(nbuf)] if with_mask else None
+        self.stream = torch.cuda.Stream(device=dev)
+        # the device buffers may have been handed out while kernels already queued on the current stream (the previous run's
+        # noise copies / step graph) still read them: the upload stream must not start writing before the current stream has
+        # reached this point
+        self.stream.wait_stream(torch.cuda.current_stream())
+        self.noise.record_stream(self.stream)
+        if self.qnoise is not None:
+            self.qnoise.record_stream(self.stream)
+        self.events = {}
+        self.produced = 0  # chunks drawn so far
+        self.dev_index = torch.cuda.current_device()   # the drawer thread must issue its uploads on THIS device
+        self.error = None
+        self.cv = threading.Condition()
+        self.threaded = (os.environ.get("ALDM_NOISE_THREAD", "1") != "0") if threaded is None else threaded
+        self.thread = None
+        if self.threaded:
+            self.thread = threading.Thread(target=self._run, name="aldm-noise-drawer", daemon=True)
+            self.thread.start()
+
+    def _draw_into(self, dst):
+        """One reference-ordered draw into a (pinned) staging row."""
+        d = self.draw
+        if getattr(d, "into", None) is not None:
+            d.into(dst)
+        else:
+            dst.numpy()[...] = d().numpy()   # plain memcpy, no thread pool
+
+    def _produce(self, c):
+        lo, hi = self.bounds[c], self.bounds[c + 1]
+        slot = c % len(self.pin)
+        prev = self.events.get(c - len(self.pin))
+        if prev is not None:
+            prev.synchronize()  # the upload that last used this pinned slot is done
+        # Host side of the RNG contract.  The draws go STRAIGHT into the pinned staging rows (`torch.randn(out=...)`: same
+        # generator stream, no intermediate tensor): a 1 MB `Tensor.copy_` through torch's intra-op thread pool costs
+        # ~20 ms on a many-core host (measured: 19 ms with 8 threads on 8 busy vCPUs vs 0.02 ms with 4).
+        for s in range(lo, hi):  # reference order per step
+            if self.with_mask and self.mask_first:
+                self._draw_into(self.qpin[slot][s - lo])
+            self._draw_into(self.pin[slot][s - lo])
+            if self.temperature != 1.0:
+                self.pin[slot][s - lo].mul_(self.temperature)
+            if self.with_mask and not self.mask_first:
+                self._draw_into(self.qpin[slot][s - lo])
+        with torch.cuda.stream(self.stream):
+            self.noise[lo:hi].copy_(self.pin[slot][:hi - lo], non_blocking=True)
+            if self.with_mask:
+                self.qnoise[lo:hi].copy_(self.qpin[slot][:hi - lo], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(self.stream)
+        return ev
+
+    def _run(self):   # drawer thread
+        try:
+            torch.cuda.set_device(self.dev_index)
+            for c in range(len(self.bounds) - 1):
+                ev = self._produce(c)
+                with self.cv:
+                    self.events[c] = ev
+                    self.produced = c + 1
+                    self.cv.notify_all()
+        except BaseException as e:  # surfaced by the launching thread's next wait()
+            with self.cv:
+                self.error = e
+                self.cv.notify_all()
+
+    def produce_next(self):
+        """Unthreaded mode (ALDM_NOISE_THREAD=0 / tests): draw + upload the next chunk on the calling thread."""
+        if self.threaded:
+            return
+        c = self.produced
+        if c + 1 >= len(self.bounds):
+            return
+        self.events[c] = self._produce(c)
+        self.produced = c + 1
+
+    def wait(self, i):
+        """Make the current stream wait for step i's noise; returns True when i opens a chunk."""
+        c = 0 if i == 0 else 1 + (i - 1) // self.chunk
+        if self.threaded:
+            with self.cv:
+                while self.produced <= c and self.error is None:
+                    self.cv.wait(timeout=60.0)
+                if self.error is not None:
+                    raise RuntimeError(f"noise drawer thread failed: {self.error!r}")
+        else:
+            while self.produced <= c:
+                self.produce_next()
+        first = i == self.bounds[c]
+        if first:
+            torch.cuda.current_stream().wait_event(self.events[c])
+        return first
+
+    def close(self):
+        """Join the drawer: every draw of the run has been consumed from the generator (callers draw again afterwards)."""
+        if self.thread is not None:
+            self.thread.join()
+            self.thread = None
+            if self.error is not None:
+                raise RuntimeError(f"noise drawer thread failed: {self.error!r}")
+
+
+def host_drawer(shape, noise_shard=None):
+    """draw() -> one `torch.randn(shape)` from the host default generator, in the reference's order; draw.into(dst) writes
+    it into `dst`.  noise_shard = (global_batch, row_offset): a prompt-sharded run draws the GLOBAL batch like the
+    single-process reference and keeps rows [offset, offset + shape[0]) (dist.py); with several candidates per prompt
+    the second element is the index tensor of the rank's rows (dist.candidate_rows) instead of an offset."""
+    shape = tuple(shape)
+    if noise_shard is None:
+        def draw():
+            return torch.randn(shape)
+
+        def into(dst):
+            torch.randn(shape, out=dst)
+    else:
+        gB, off = noise_shard
+        gshape = (gB,) + shape[1:]
+        if torch.is_tensor(off):
+            assert off.numel() == shape[0]
+            pick = lambda t: t.index_select(0, off)
+        else:
+            pick = lambda t: t[off:off + shape[0]]
+
+        def draw():
+            return pick(torch.randn(gshape)).contiguous()
+
+        def into(dst):
+            dst.numpy()[...] = pick(torch.randn(gshape)).numpy()
+    draw.into = into
+    return draw
+
+
+def check_guidance_rescale(phi) -> float:
+    """The `guidance_rescale` argument of the samplers and the pipeline as a float: phi of Lin et al. 2023 (section 3.4), in [0, 1];
+    0 is off."""
+    try:
+        phi = float(phi)
+    except (TypeError, ValueError):
+        raise ValueError(f"guidance_rescale must be a number in [0, 1], got {phi!r}")
+    if not (np.isfinite(phi) and 0.0 <= phi <= 1.0):
+        raise ValueError(f"guidance_rescale must be finite and in [0, 1], got {phi!r}")
+    return phi
+
+
+def guidance_table(rows, scale, use_cfg, phi=0.0):
+    """Pure host function: a sampler's [S, 8] fp32 coefficient table from its [S, 5] rows.  Column 5 = the guidance scale; column
+    6 = 1 when the step kernel combines eps[2, n] itself; column 7 = phi.  With guidance rescale on (guidance and phi > 0) the
+    combine moves into ops.cfg_rescale_indexed, which reads columns 5 and 7, and the step kernel gets a combined eps[n]: column 6 = 0."""
+    rescale = bool(use_cfg) and phi > 0.0
+    coef = torch.zeros(rows.shape[0], 8)
+    coef[:, :5] = rows
+    coef[:, 5] = float(scale)
+    coef[:, 6] = 1.0 if use_cfg and not rescale else 0.0
+    coef[:, 7] = float(phi) if rescale else 0.0
+    return coef
+
+
+def check_t_start(t_start, timesteps, schedule_len):
+    """The `t_start=` keyword of the three samplers (the name of `DDIMSampler.decode`'s parameter): None, or the number k of
+    schedule entries to run — indices k-1 ... 0 — from x_T, 1 <= k <= the schedule's length; not together with `timesteps`, whose
+    count goes through the reference's float arithmetic."""
+    if t_start is None:
+        return None
+    if timesteps is not None:
+        raise ValueError(f"t_start={t_start!r} and timesteps={timesteps!r} both name where to start: pass one")
+    if isinstance(t_start, bool) or not isinstance(t_start, (int, np.integer)) or not 1 <= t_start <= schedule_len:
+        raise ValueError(f"t_start must be an integer in [1, {schedule_len}] (the schedule's length), got {t_start!r}")
+    return int(t_start)
+
+
+
+def ddim_step_rows(sigmas, alphas, alphas_prev, sqrt_one_minus_alphas):
+    """Pure host function: the [S, 5] fp32 rows {sqrt(1 - a_t), sqrt(a_t), sqrt(1 - a_prev - sigma_t^2), sqrt(a_prev), sigma_t} of
+    DDIM's update (the row layout of ops.ddim_step), one per schedule index, with the reference's roundings (ddim.py:330-353,
+    plms.py:319-338): a_t, a_prev, sigma_t and sqrt(1 - a_t) become fp32 via torch.full; the other square roots are fp32 tensor ops."""
+    rows = []
+    for i in range(len(alphas)):
+        a_t = torch.full((1,), float(alphas[i]))
+        ap = torch.full((1,), float(alphas_prev[i]))
+        sg = torch.full((1,), float(sigmas[i]))
+        som = torch.full((1,), float(sqrt_one_minus_alphas[i]))
+        rows.append(torch.cat([som, a_t.sqrt(), (1.0 - ap - sg ** 2).sqrt(), ap.sqrt(), sg]))
+    return torch.stack(rows)
+
+
+def log_step(i, total_steps, log_every_t, x_cur, pred_x0, intermediates, callback=None, img_callback=None):
+    """The tail of step i of a sampling loop (ddim.py:244-260): the two callbacks, then the step's state into `intermediates`
+    every `log_every_t` schedule indices and at the run's first step."""
+    if callback:
+        callback(i)
+    if img_callback:
+        img_callback(pred_x0, i)
+    index = total_steps - i - 1
+    if index % log_every_t == 0 or index == total_steps - 1:
+        intermediates["x_inter"].append(x_cur.clone())
+        intermediates["pred_x0"].append(pred_x0.clone())
+
+
+class SamplerBase(object):
+    """Constructor, schedule, run plan and UNet pass of the three samplers.  A subclass adds its coefficient rows in
+    `make_schedule`, its `sample` and its loop."""
+
+    # why `ddim_use_original_steps=True` is refused (the tail of _refuse's message)
+    ORIGINAL_STEPS = "is not supported"
+
+    def __init__(self, model, schedule="linear", **kwargs):
+        super().__init__()
+        self.model = model
+        self.ddpm_num_timesteps = model.num_timesteps
+        self.schedule = schedule
+        self.use_graph = os.environ.get("ALDM_NO_GRAPH", "0") != "1"
+        # (global_batch, row_offset) when this process samples one shard of a larger batch (dist.py)
+        self.noise_shard = getattr(model, "noise_shard", None)
+
+    def register_buffer(self, name, attr):
+        setattr(self, name, attr)
+
+    def make_schedule(self, ddim_num_steps, ddim_discretize="uniform", ddim_eta=0.0, verbose=True):
+        """ddim.py:33-91 / plms.py:27-89 (host side, float tables only): the timestep grid, the abar tables, DDIM's sigma and abar
+        per grid entry."""
+        self.ddim_timesteps = make_ddim_timesteps(ddim_discretize, ddim_num_steps, self.ddpm_num_timesteps, verbose)
+        alphas_cumprod = self.model.alphas_cumprod.detach().float().cpu()
+        assert alphas_cumprod.shape[0] == self.ddpm_num_timesteps, "alphas have to be defined for each timestep"
+        self.register_buffer("alphas_cumprod", alphas_cumprod)
+        self.register_buffer("sqrt_alphas_cumprod", torch.sqrt(alphas_cumprod))
+        self.register_buffer("sqrt_one_minus_alphas_cumprod", torch.sqrt(1.0 - alphas_cumprod))
+        sig, a, a_prev = make_ddim_sampling_parameters(alphas_cumprod, self.ddim_timesteps, ddim_eta, verbose)
+        self.register_buffer("ddim_sigmas", sig)
+        self.register_buffer("ddim_alphas", a)
+        self.register_buffer("ddim_alphas_prev", a_prev)
+
+    def _refuse(self, ddim_use_original_steps, quantize_denoised, score_corrector, noise_dropout):
+        name = type(self).__name__
+        if ddim_use_original_steps:
+            raise NotImplementedError(f"{name}(HIP): ddim_use_original_steps=True {self.ORIGINAL_STEPS}")
+        if quantize_denoised or score_corrector is not None or noise_dropout != 0.0:
+            raise NotImplementedError(f"{name}(HIP): option not used by the AudioLDM2 pipeline")
+
+    def model_output(self, x, t_row, b, cond, uncond, use_cfg, prepared):
+        """The UNet pass of one step: eps [2, b, ...] = [uncond ; cond] under guidance (combined inside the step kernel, or by
+        ops.cfg_rescale_indexed), else eps [b, ...].  t_row: the step's timestep as floats, one entry per UNet row.  Guidance is ONE
+        pass over 2b samples when the model has `apply_model_cfg` — asked at every call: it may be set on an instance — where the
+        reference runs two (ddim.py:293-296)."""
+        if not use_cfg:
+            return self.model.apply_model(x, t_row[:b].long(), cond).contiguous()
+        if hasattr(self.model, "apply_model_cfg"):
+            return self.model.apply_model_cfg(x, t_row, cond, uncond, prepared=prepared)
+        tl = t_row[:b].long()
+        return torch.stack([self.model.apply_model(x, tl, uncond), self.model.apply_model(x, tl, cond)]).contiguous()
+
+    def plan_run(self, cond, shape, x_T, t_start, timesteps, table, unconditional_guidance_scale, unconditional_conditioning,
+                 guidance_rescale, mask, x0):
+        """Everything a sampling loop needs before its first step, as one object.  `table(total_steps, use_cfg)` is the sampler's
+        own [total_steps, 8] host coefficient table in loop order (i = 0 is the noisiest step, index = total_steps - 1).
+
+        The cut of the schedule: `t_start=k` keeps exactly its first k entries, as `decode` cuts it (ddim.py:466-467; see
+        check_t_start); `timesteps` keeps its first int(min(timesteps / S, 1) * S) - 1 entries (ddim.py:198-206).  `total_steps`
+        may be 0 (`timesteps` <= one interval): the reference's loop then runs zero iterations and returns x_T, and nothing past
+        `img` is built.
+
+        RNG contract R: x_T is the host generator's first draw of the run, made only when x_T is not given; `draw` makes the
+        loop's later ones.  A start latent that already lives on the device (audio-to-audio) stays there.  Host -> device copies,
+        in this order: img, coef, t_tab, mask_d, x0_d, blend_coef, then the model's prepare_cfg."""
+        dev = torch.device("cuda")
+        shape = tuple(shape)
+        ts = self.ddim_timesteps
+        t_start = check_t_start(t_start, timesteps, ts.shape[0])
+        if t_start is not None:
+            ts = ts[:t_start]
+        if timesteps is not None:
+            subset_end = int(min(timesteps / ts.shape[0], 1) * ts.shape[0]) - 1
+            ts = ts[:subset_end]
+        total_steps = ts.shape[0]
+        use_cfg = not (unconditional_conditioning is None or unconditional_guidance_scale == 1.0)
+        p = SimpleNamespace(total_steps=total_steps, use_cfg=use_cfg, mask_d=None, x0_d=None, blend_coef=None, prepared=None)
+        p.time_range = np.flip(ts).copy()   # own storage, positive strides: from_numpy refuses the flipped view, even of one entry
+        # guidance rescale: the combine and the per-sample rescale run in a launch of their own in front of the step kernel
+        p.rescale = use_cfg and guidance_rescale > 0.0
+        p.draw = host_drawer(shape, self.noise_shard)
+        p.img = (p.draw().to(dev) if x_T is None else x_T.detach().float().to(dev)).contiguous()
+        if total_steps == 0:
+            return p
+        p.coef = table(total_steps, use_cfg).to(dev)
+        tr = torch.from_numpy(p.time_range)
+        p.t_tab = tr.float()[:, None].repeat(1, (2 if use_cfg else 1) * shape[0]).to(dev).contiguous()
+        if mask is not None:
+            assert x0 is not None
+            p.mask_d = mask.float().to(dev).expand(shape).contiguous()
+            p.x0_d = x0.float().to(dev).contiguous()
+            p.blend_coef = torch.stack([self.sqrt_alphas_cumprod[tr], self.sqrt_one_minus_alphas_cumprod[tr]],
+                                       1).contiguous().to(dev)  # [S, 2] = {sqrt(abar_t), sqrt(1 - abar_t)}
+        if use_cfg and hasattr(self.model, "apply_model_cfg") and hasattr(self.model, "prepare_cfg"):
+            p.prepared = self.model.prepare_cfg(cond, unconditional_conditioning)
+        return p

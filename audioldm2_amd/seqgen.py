@@ -269,9 +269,9 @@ class Sequence2AudioMAE(nn.Module):
         out = self._forward_positions(x, 0, kc, vc, keymask)
         tok = out[:, -1:, :].contiguous()
         # every later token: one decode step that reads / advances device-side state only.  Long generations (the speech
-        # model: 512 tokens) replay it as one HIP graph (eager the first time, captured the second: ddim.GraphStepper);
+        # model: 512 tokens) replay it as one HIP graph (eager the first time, captured the second: sampling.GraphStepper);
         # the 8-token text-to-audio configurations run the same step eagerly — a capture is not worth 7 steps
-        from .ddim import GraphStepper
+        from .sampling import GraphStepper
         toks = torch.empty((B, steps, N_EMBD), device=dev)
         toks[:, 0:1] = tok
         ps = torch.tensor([P, 1], device=dev, dtype=torch.long)      # (position, output slot): advanced together, one launch per token
@@ -289,8 +289,7 @@ class Sequence2AudioMAE(nn.Module):
             for _ in range(steps - 1):
                 run()
         finally:
-            run.fn = None          # break the closure cycle: the graph and its pool go with this call, not with a later collection
-            run.graph = None
+            run.release()          # break the closure cycle: the graph and its pool go with this call, not with a later collection
             self._decode_fast = None   # a later direct `_decode_one` reads $ALDM_SEQGEN_DECODE again
         return toks, cond_dict
 

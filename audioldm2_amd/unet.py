@@ -440,7 +440,7 @@ class UNetModel(nn.Module):
     def invalidate_packed(self):
         """Drop every re-laid-out weight copy, cached context projection and captured step graph (call
         after mutating parameters)."""
-        from .ddim import drop_graph_entries
+        from .sampling import drop_graph_entries
         drop_graph_entries(self._graph_cache)   # frees the graphs now, not at some later cyclic collection
         for m in self.modules():
             if hasattr(m, "_pk"):
@@ -451,7 +451,7 @@ class UNetModel(nn.Module):
     def drop_step_caches(self):
         """Drop what depends on the matrix-core mode but not on the weights: the captured step graph and the cached
         cross-attention K/V projections (call after ops.set_mma(); the packed weights keep both split images)."""
-        from .ddim import drop_graph_entries
+        from .sampling import drop_graph_entries
         drop_graph_entries(self._graph_cache)
         for m in self.modules():
             if hasattr(m, "_kv"):
