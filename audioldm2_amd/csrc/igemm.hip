@@ -41,6 +41,11 @@ int igemm_dma_os_default_stages(int KT, int parts);
 // staged in LDS once for all nine taps
 int igemm_launch_dma_halo(int BM, int BN, int nstb, int wm, int parts, bool f16, int maxch, dim3 grid, hipStream_t st, const IgemmK& p);
 int igemm_dma_halo_maxch(int BM, int BN, int nstb, int wm, int parts, int nch);
+// ... and which (tile, ring) instantiations of the classic, loader-wave and halo-patch kernels carry the compile-time epilogue forms
+// (igemm_dma_forms.hip, igemm_dma_lw_forms.hip, igemm_dma_halo_forms.hip)
+bool igemm_dma_form_ok(int BM, int BN, int nst, int parts);
+bool igemm_dma_lw_form_ok(int BM, int BN, int nst, int parts);
+bool igemm_dma_halo_form_ok(int BM, int BN, int nstb, int wm, int parts, int maxch);
 
 // split-K reduce: out = epi(sum_s ws[z][s][m][n]) — fixed summation order, one thread per element
 // quad (N % 4 == 0 is required for split-K).
@@ -258,6 +263,51 @@ extern "C" int aldm_igemm_mma(int mode) {
     return prev;
 }
 
+// compile-time epilogue forms (igemm_epilogue.h): process wide, like the attention schedule — -1 = default ($ALDM_EPI_FORMS, read
+// once, else on), 0 = every launch on the generic epilogue, 1 = forms wherever plan_epilogue_form allows
+static std::atomic<int> g_epi_forms{-1};
+static int epi_forms_on() {
+    static const int env_on = [] {
+        const char* e = getenv("ALDM_EPI_FORMS");
+        return (e && e[0] == '0' && e[1] == 0) ? 0 : 1;
+    }();
+    const int v = g_epi_forms.load(std::memory_order_relaxed);
+    return v < 0 ? env_on : v;
+}
+extern "C" int aldm_igemm_epilogue_forms(int on) {
+    const int prev = epi_forms_on();
+    g_epi_forms.store(on == 0 || on == 1 ? on : -1, std::memory_order_relaxed);
+    return prev;
+}
+
+// The epilogue form of a prepared launch.  A form needs: a DMA-fed kernel instantiation that carries the forms; the plain epilogue
+// with no split-K, activation, scaling, accumulation or row remap; bf16 operands, and a split-image output (if any) in the same
+// format — the forms store it with the kernel's own part count; everything the epilogue touches addressable as float4 (what the
+// generic form computes into `vec`, plus the bias and the row bias, which the forms load as vectors too).  A residual AND a row
+// bias in one launch (no such launch in the models) stays generic.
+static int plan_epilogue_form(const IgemmK& p, int BM, int BN) {
+    const aldm_igemm_desc& d = p.d;
+    if (!epi_forms_on() || !p.dma || d.a_fmt != ALDM_FMT_BF16) return ALDM_EPI_FORM_GENERIC;
+    const bool inst = p.ws == 0   ? igemm_dma_form_ok(BM, BN, p.nst, d.split_parts)
+                      : p.ws == 2 ? igemm_dma_lw_form_ok(BM, BN, p.nst, d.split_parts)
+                      : p.ws == 4 ? igemm_dma_halo_form_ok(BM, BN, p.nst, p.ws_blocks, d.split_parts, p.os_rows)
+                                  : false;
+    if (!inst) return ALDM_EPI_FORM_GENERIC;
+    if (d.epi_mode != ALDM_EPI_PLAIN || p.splits != 1 || d.act != ALDM_ACT_NONE || d.alpha != 1.0f || d.accumulate ||
+        d.out_mul > 0 || d.batch != 1)
+        return ALDM_EPI_FORM_GENERIC;
+    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+    if ((d.N & 3) != 0 || (d.ldo & 3) != 0 || (d.stride_o & 3) != 0 || !al16(d.out) || !al16(d.res) || !al16(d.bias) ||
+        !al16(d.rowbias) || (d.rowbias && (p.rb_ld & 3) != 0))
+        return ALDM_EPI_FORM_GENERIC;
+    if (d.out_split && (d.out_split_fmt != ALDM_FMT_BF16 || d.out_split_parts != d.split_parts)) return ALDM_EPI_FORM_GENERIC;
+#ifdef ALDM_TEST_HOOKS
+    if (g_debug_drop_product.load(std::memory_order_relaxed)) return ALDM_EPI_FORM_GENERIC;   // (the 5-product kernel has no forms)
+#endif
+    if (d.res && d.rowbias) return ALDM_EPI_FORM_GENERIC;
+    return d.res ? ALDM_EPI_FORM_RES : (d.rowbias ? ALDM_EPI_FORM_ROWBIAS : ALDM_EPI_FORM_PLAIN);
+}
+
 static int pre_mode_of(const aldm_igemm_desc& d) {
     if (d.pre_scale == nullptr && d.pre_act == ALDM_ACT_NONE) return PRE_NONE;
     if (d.pre_scale != nullptr && d.pre_act == ALDM_ACT_NONE) return PRE_AFFINE;
@@ -329,6 +379,7 @@ static int igemm_prepare(const aldm_igemm_desc* dd, IgemmK& p, int& BM, int& BN)
     ALDM_CHECK(dd != nullptr, "aldm_igemm: null descriptor");
     p.d = *dd;
     aldm_igemm_desc& d = p.d;
+    p.epi_form = ALDM_EPI_FORM_GENERIC;   // (aldm_igemm decides after the kernel family is known: plan_epilogue_form)
     ALDM_CHECK((d.x1 || d.a_split) && d.w && (d.out || d.out_split), "aldm_igemm: null x1/w/out");
     if (!d.x1) d.x1 = reinterpret_cast<const float*>(d.a_split);  // never dereferenced on the DMA path
     if (d.split_parts == 0) d.split_parts = 3;
@@ -760,6 +811,13 @@ extern "C" int aldm_igemm_plan_stages(const aldm_igemm_desc* dd) {
     return p.dma ? p.nst + 100 * p.ws : 0;
 }
 
+extern "C" int aldm_igemm_plan_epilogue(const aldm_igemm_desc* dd) {
+    IgemmK p;
+    int BM, BN;
+    if (igemm_prepare(dd, p, BM, BN)) return -1;
+    return plan_epilogue_form(p, BM, BN);
+}
+
 extern "C" int64_t aldm_igemm_ws_floats(const aldm_igemm_desc* dd) {
     if (!dd) return 0;
     // ask with an "infinite" dummy workspace to learn the split the heuristic wants
@@ -777,6 +835,7 @@ extern "C" int aldm_igemm(const aldm_igemm_desc* dd, void* stream) {
     int BM, BN;
     int rc = igemm_prepare(dd, p, BM, BN);
     if (rc) return rc;
+    p.epi_form = plan_epilogue_form(p, BM, BN);
     const aldm_igemm_desc& d = p.d;
     dim3 grid((unsigned)(p.tiles_m * p.tiles_n), (unsigned)p.splits, (unsigned)d.batch);
     hipStream_t st = (hipStream_t)stream;

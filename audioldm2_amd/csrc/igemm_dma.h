@@ -92,7 +92,8 @@ __device__ __forceinline__ void wait_vmcnt() {
 // DROP (test hook, aldm_debug_drop_product): leave out the first — smallest — partial product (hi_a x lo_w).  The result is a
 // deliberately broken "5-product" GEMM, ~1e-5 off: tests/test_dma_gpu.py asserts that it FAILS the fp32-grade bar, i.e. that the
 // bar would catch a kernel that silently lost a product.  Instantiated for ONE tile only (64x128, 2 stages, 3 parts).
-template <int BM, int BN, int NST, int WM = 2, int NP = 3, bool DROP = false, bool F16 = false>
+// FORM = ALDM_EPI_FORM_*: the compile-time epilogue form (igemm_epilogue.h); 0 = the generic run-time epilogue
+template <int BM, int BN, int NST, int WM = 2, int NP = 3, bool DROP = false, bool F16 = false, int FORM = ALDM_EPI_FORM_GENERIC>
 __global__ __launch_bounds__(128 * WM, dma_blocks_per_cu(BM, BN, NST, NP) * (WM / 2))
 void igemm_dma_kernel(const IgemmK p) {
     constexpr int WN = 2, NW = WM * WN;
@@ -105,6 +106,7 @@ void igemm_dma_kernel(const IgemmK p) {
     constexpr int NPROD = NP == 3 ? 6 : 3;    // bf16 partial products per fp32 product
     static_assert(NP == 2 || NP == 3, "2 or 3 parts");
     static_assert(!F16 || NP == 2, "fp16 images have two parts");
+    static_assert(!F16 || FORM == ALDM_EPI_FORM_GENERIC, "the epilogue forms write bf16 images");
     static_assert(BM % (16 * NW) == 0 && (4 * NP * (BN / 64)) % NW == 0, "DMA chunks must divide among the waves");
     static_assert(NST >= 2 && NST <= 8 && (NST - 1) * D <= 63, "ring depth / vmcnt range");
     static_assert(NW * 32 * (NT * 32 + 4) * 4 <= NST * STG * 16, "epilogue staging must fit the ring");
@@ -332,6 +334,12 @@ void igemm_dma_kernel(const IgemmK p) {
     };
 
     // ---- K loop ----------------------------------------------------------------------------------------------
+    // Epilogue form: bias, residual and row-bias quads of all this wave's slabs.  The same waves issue the ring's LDS-DMA and
+    // count vmcnt by hand, so the prefetch goes in front of the FIRST ring issue: loads return in order, every counted wait below
+    // allows only the youngest N operations to be outstanding, hence the first of them already covers these loads and the ring's
+    // accounting never sees them.  They fly next to k-tile 0's DMA.
+    EpiPre<MT, NT, FORM> epre;
+    if constexpr (FORM != ALDM_EPI_FORM_GENERIC) epi_form_prefetch(p, epre, m0, n0, wm, wn, lane);
 #pragma unroll
     for (int s = 0; s < NST; ++s)
         if (s < nk) issue(s);
@@ -402,7 +410,10 @@ void igemm_dma_kernel(const IgemmK p) {
     return;
 #endif
     unscale_acc<F16>(acc, d.acc_scale);
-    igemm_epilogue<MT, NT>(p, acc, reinterpret_cast<float*>(&smem[0]), m0, n0, wave, wm, wn, lane, 0, split);
+    if constexpr (FORM != ALDM_EPI_FORM_GENERIC)
+        igemm_epilogue_form<MT, NT, NP, FORM>(p, acc, epre, reinterpret_cast<float*>(&smem[0]), m0, n0, wave, wm, wn, lane);
+    else
+        igemm_epilogue<MT, NT>(p, acc, reinterpret_cast<float*>(&smem[0]), m0, n0, wave, wm, wn, lane, 0, split);
 }
 
 }  // namespace aldm

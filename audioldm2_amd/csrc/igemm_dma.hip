@@ -21,6 +21,9 @@ bool igemm_dma_config_ok(int BM, int BN, int nst, int parts) {
 std::atomic<int> g_debug_drop_product{0};
 #endif
 
+// igemm_dma_forms.hip: the instantiations with a compile-time epilogue form
+int igemm_launch_dma_form(int BM, int BN, int nst, int form, dim3 grid, hipStream_t st, const IgemmK& p);
+
 int igemm_launch_dma(int BM, int BN, int nst, int parts, bool f16, dim3 grid, hipStream_t st, const IgemmK& p) {
 #ifdef ALDM_TEST_HOOKS
     if (g_debug_drop_product.load(std::memory_order_relaxed)) {   // (aldm_igemm has checked the tile)
@@ -29,6 +32,7 @@ int igemm_launch_dma(int BM, int BN, int nst, int parts, bool f16, dim3 grid, hi
         return 0;
     }
 #endif
+    if (p.epi_form != ALDM_EPI_FORM_GENERIC) return igemm_launch_dma_form(BM, BN, nst, p.epi_form, grid, st, p);
 #define ALDM_DMA(BM_, BN_, NST_, NP_) \
     hipLaunchKernelGGL((igemm_dma_kernel<BM_, BN_, NST_, 2, NP_>), grid, dim3(256), 0, st, p)
 #define ALDM_DMA8(BM_, BN_, NST_, NP_) \

@@ -48,7 +48,8 @@ constexpr int halo_lds_slots(int BN, int NSTB, int NP, int MAXCH) {
     return 2 * MAXCH * NP * 64 + NSTB * BN * 4 * NP + NP * 64;   // two patches, the weight ring, the zero region
 }
 
-template <int BM, int BN, int NSTB, int WM, int NP, int MAXCH, bool F16 = false>
+// FORM = ALDM_EPI_FORM_*: the compile-time epilogue form (igemm_epilogue.h); 0 = the generic run-time epilogue
+template <int BM, int BN, int NSTB, int WM, int NP, int MAXCH, bool F16 = false, int FORM = ALDM_EPI_FORM_GENERIC>
 __global__ __launch_bounds__(128 * WM, WM / 2)
 void igemm_dma_halo_kernel(const IgemmK p) {
     constexpr int WN = 2, NW = WM * WN;
@@ -63,6 +64,7 @@ void igemm_dma_halo_kernel(const IgemmK p) {
     constexpr int ATILES = 11 - NSTB;              // patch-piece slots per channel block
     constexpr int NPROD = NP == 3 ? 6 : 3;
     static_assert(NP == 2 || NP == 3, "2 or 3 parts");
+    static_assert(!F16 || FORM == ALDM_EPI_FORM_GENERIC, "the epilogue forms write bf16 images");
     static_assert((4 * NP * (BN / 64)) % NW == 0, "weight pieces must divide among the waves");
     static_assert(NSTB >= 2 && NSTB <= 6 && (NSTB - 1) * D <= 63, "ring depth / vmcnt range");
     static_assert(NW * 32 * (NT * 32 + 4) * 4 <= Z0 * 16, "epilogue staging must fit");
@@ -270,6 +272,10 @@ void igemm_dma_halo_kernel(const IgemmK p) {
     };
 
     // ---- prologue: the zero region, the whole patch of the first channel block, slot 0 of the second, NSTB weight tiles ----------
+    // Epilogue form: bias, residual and row-bias quads of all this wave's slabs, in front of the FIRST LDS-DMA issue: loads return
+    // in order, so the prologue's wait_vmcnt<0> below covers them and no counted wait of the K loop ever sees them (igemm_dma.h).
+    EpiPre<MT, NT, FORM> epre;
+    if constexpr (FORM != ALDM_EPI_FORM_GENERIC) epi_form_prefetch(p, epre, m0, n0, wm, wn, lane);
     if (wave < NP)
         __builtin_amdgcn_global_load_lds((gptr_t)(zero + lane * 16), (lptr_t)&smem[Z0 + wave * 64], 16, 0, 0);
     for (int id = wave; id < NCH * NP; id += NW) issue_piece(prep_patch_piece(id, 0, true));
@@ -361,7 +367,10 @@ void igemm_dma_halo_kernel(const IgemmK p) {
     return;
 #endif
     unscale_acc<F16>(acc, d.acc_scale);
-    igemm_epilogue<MT, NT>(p, acc, reinterpret_cast<float*>(&smem[0]), m0, n0, wave, wm, wn, lane, 0, split);
+    if constexpr (FORM != ALDM_EPI_FORM_GENERIC)
+        igemm_epilogue_form<MT, NT, NP, FORM>(p, acc, epre, reinterpret_cast<float*>(&smem[0]), m0, n0, wave, wm, wn, lane);
+    else
+        igemm_epilogue<MT, NT>(p, acc, reinterpret_cast<float*>(&smem[0]), m0, n0, wave, wm, wn, lane, 0, split);
 }
 
 }  // namespace aldm

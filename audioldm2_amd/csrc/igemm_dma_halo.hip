@@ -34,7 +34,11 @@ int igemm_dma_halo_maxch(int BM, int BN, int nstb, int wm, int parts, int nch) {
     return best;
 }
 
+// igemm_dma_halo_forms.hip: the instantiations with a compile-time epilogue form
+int igemm_launch_dma_halo_form(int BM, int BN, int nstb, int wm, int maxch, int form, dim3 grid, hipStream_t st, const IgemmK& p);
+
 int igemm_launch_dma_halo(int BM, int BN, int nstb, int wm, int parts, bool f16, int maxch, dim3 grid, hipStream_t st, const IgemmK& p) {
+    if (p.epi_form != ALDM_EPI_FORM_GENERIC) return igemm_launch_dma_halo_form(BM, BN, nstb, wm, maxch, p.epi_form, grid, st, p);
     if (f16) {   // "f16x3" images: the 2-part instantiations on the fp16 matrix instruction
 #define X(BM_, BN_, NST_, WM_, NP_, CH_)                                                                                   \
     if constexpr (NP_ == 2) {                                                                                              \

@@ -12,7 +12,8 @@
 
 namespace aldm {
 
-template <int BM, int BN, int NST, int WM, int NP, int BPC, bool F16 = false>
+// FORM = ALDM_EPI_FORM_*: the compile-time epilogue form (igemm_epilogue.h); 0 = the generic run-time epilogue
+template <int BM, int BN, int NST, int WM, int NP, int BPC, bool F16 = false, int FORM = ALDM_EPI_FORM_GENERIC>
 __global__ __launch_bounds__(256 * WM, BPC * WM)
 void igemm_dma_lw_kernel(const IgemmK p) {
     constexpr int WN = 2, NW = WM * WN;
@@ -24,6 +25,7 @@ void igemm_dma_lw_kernel(const IgemmK p) {
     constexpr int D = NP * RA + NB;
     constexpr int NPROD = NP == 3 ? 6 : 3;
     static_assert(NP == 2 || NP == 3, "2 or 3 parts");
+    static_assert(!F16 || FORM == ALDM_EPI_FORM_GENERIC, "the epilogue forms write bf16 images");
     static_assert(BM % (16 * NW) == 0 && (4 * NP * (BN / 64)) % NW == 0, "DMA chunks must divide among the loader waves");
     static_assert(NST >= 2 && NST <= 8 && (NST - 1) * D <= 63, "ring depth / vmcnt range");
     static_assert(NW * 32 * (NT * 32 + 4) * 4 <= NST * STG * 16, "epilogue staging must fit the ring");
@@ -210,6 +212,10 @@ void igemm_dma_lw_kernel(const IgemmK p) {
                     acc[i][j] = mfma_32x32x16<F16>(f.a[i][PA_[q]], f.b[j][PB_[q]], acc[i][j]);
     };
     constexpr int NMF = NPROD * MT * NT, NRD = NP * (MT + NT);
+    // Epilogue form: bias, residual and row-bias quads of all this wave's slabs, fetched here — an MMA wave issues no other
+    // vector-memory instruction before its epilogue (the loader waves own the ring and its vmcnt), so they land under the K loop.
+    EpiPre<MT, NT, FORM> epre;
+    if constexpr (FORM != ALDM_EPI_FORM_GENERIC) epi_form_prefetch(p, epre, m0, n0, wm, wn, lane);
     __builtin_amdgcn_s_barrier();                           // P
     Frag f0, f1;
     read_frags(f0, 0, 0);
@@ -246,7 +252,10 @@ void igemm_dma_lw_kernel(const IgemmK p) {
     __builtin_amdgcn_s_waitcnt((7 << 4) | (3 << 14) | 15);   // lgkmcnt(0)
     __builtin_amdgcn_s_barrier();   // every MMA wave is past its last fragment read: the ring becomes epilogue staging
     unscale_acc<F16>(acc, d.acc_scale);
-    igemm_epilogue<MT, NT>(p, acc, reinterpret_cast<float*>(&smem[0]), m0, n0, wave, wm, wn, lane, 0, split);
+    if constexpr (FORM != ALDM_EPI_FORM_GENERIC)
+        igemm_epilogue_form<MT, NT, NP, FORM>(p, acc, epre, reinterpret_cast<float*>(&smem[0]), m0, n0, wave, wm, wn, lane);
+    else
+        igemm_epilogue<MT, NT>(p, acc, reinterpret_cast<float*>(&smem[0]), m0, n0, wave, wm, wn, lane, 0, split);
 }
 
 }  // namespace aldm

@@ -21,14 +21,23 @@ bool igemm_dma_lw_config_ok(int BM, int BN, int nst, int parts) {
     return false;
 }
 
-int igemm_launch_dma_lw(int BM, int BN, int nst, int parts, bool f16, dim3 grid, hipStream_t st, const IgemmK& p) {
-    // blocks per CU the registers are budgeted for: 2 (128 VGPRs per wave: the 64-row / 64-column tiles fit, bar a few
-    // epilogue spills) unless the ring leaves room for one block only or the tile needs more registers (128x128).
-    // $ALDM_LW_BPC=1 forces one block per CU everywhere (A/B).
+int igemm_dma_lw_env_bpc() {
     static const int env_bpc = [] {
         const char* e = getenv("ALDM_LW_BPC");
         return e ? atoi(e) : 0;
     }();
+    return env_bpc;
+}
+
+// igemm_dma_lw_forms.hip: the instantiations with a compile-time epilogue form
+int igemm_launch_dma_lw_form(int BM, int BN, int nst, int form, dim3 grid, hipStream_t st, const IgemmK& p);
+
+int igemm_launch_dma_lw(int BM, int BN, int nst, int parts, bool f16, dim3 grid, hipStream_t st, const IgemmK& p) {
+    // blocks per CU the registers are budgeted for: 2 (128 VGPRs per wave: the 64-row / 64-column tiles fit, bar a few
+    // epilogue spills) unless the ring leaves room for one block only or the tile needs more registers (128x128).
+    // $ALDM_LW_BPC=1 forces one block per CU everywhere (A/B).
+    const int env_bpc = igemm_dma_lw_env_bpc();
+    if (p.epi_form != ALDM_EPI_FORM_GENERIC) return igemm_launch_dma_lw_form(BM, BN, nst, p.epi_form, grid, st, p);
 #define ALDM_LW_H(BM_, BN_, NST_, WM_)                                                                                  \
     if (f16 && BM == BM_ && BN == BN_ && nst == NST_ && parts == 2) {                                                  \
         constexpr bool two = (160 * 1024) / dma_lds_bytes(BM_, BN_, NST_, 2) >= 2 && BM_ * BN_ < 128 * 128;            \

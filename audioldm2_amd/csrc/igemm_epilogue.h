@@ -28,6 +28,7 @@ struct IgemmK {
                                // (igemm_dma_halo.h: ws_blocks = WM, os_rows = MAXCH of the instantiation)
     int ws_blocks;
     int os_rows;               // operand-stationary kernel: rows per block (a multiple of 32)
+    int epi_form;              // ALDM_EPI_FORM_*: the compile-time epilogue form of the launch (igemm_epilogue_form below)
 };
 
 enum { PRE_NONE = 0, PRE_AFFINE = 1, PRE_AFFINE_SILU = 2, PRE_LRELU = 3, PRE_GENERIC = 4 };
@@ -467,6 +468,131 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmK& p, f32x16 (&acc)[MT
                 }
         }
         }  // itc
+    }
+}
+
+// ---- compile-time epilogue forms (round 10) ------------------------------------------------------------------------
+// igemm_epilogue above decides everything at run time, inside the per-slab loop, and fetches the residual and the row bias
+// AFTER the LDS read-back: every slab waits for an L2 / Infinity-Cache round trip with the matrix pipe already empty.  The host
+// knows the form of a launch from its descriptor (igemm.hip, plan_epilogue_form), so the common launches — plain epilogue, no
+// split-K, no activation, alpha == 1, no accumulate, no row remap, float4-addressable operands, output image in the operand's
+// bf16 format — get a straight-line form as a template parameter FORM = ALDM_EPI_FORM_*:
+//   PLAIN    v = acc + bias                         (bias == NULL: + 0, as the generic form does)
+//   ROWBIAS  v = acc + bias + rowbias[b]
+//   RES      v = (acc + bias) + res
+// then out = v and / or out_split = split<NP>([leaky_relu] v): the two outputs stay hoisted wave-uniform flags.  Same additions in
+// the same order as the generic form; alpha == 1 drops a multiplication by one.  Results are bit for bit the generic form's.
+// The optional operands of ALL the wave's slabs are fetched by epi_form_prefetch with 16-byte loads from clamped addresses, long
+// before the accumulators are final (the kernels say where), and added from registers.
+template <int NT>
+struct EpiGeom {
+    static constexpr int C4 = NT * 8;     // float4 per staged row
+    static constexpr int RPI = 64 / C4;   // rows covered by one wave-wide float4 read
+    static constexpr int IT = 32 / RPI;   // reads per 32-row slab
+};
+template <int MT, int NT, int FORM>
+struct EpiPre {
+    static constexpr bool OPT = FORM == ALDM_EPI_FORM_RES || FORM == ALDM_EPI_FORM_ROWBIAS;
+    f32x4 bias4;
+    f32x4 opt[OPT ? MT : 1][OPT ? EpiGeom<NT>::IT : 1];   // residual or row-bias quads of this lane, per slab and read
+};
+
+template <int MT, int NT, int FORM>
+__device__ __forceinline__ void epi_form_prefetch(const IgemmK& p, EpiPre<MT, NT, FORM>& q, int m0, int n0, int wm, int wn, int lane) {
+    using G = EpiGeom<NT>;
+    const aldm_igemm_desc& d = p.d;
+    const int sr = lane / G::C4;
+    const int ncol = n0 + wn * NT * 32 + (lane % G::C4) * 4;
+    const bool cok = ncol < d.N;   // N % 4 == 0 (host): the whole quad is in or out
+    q.bias4 = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (d.bias) q.bias4 = *reinterpret_cast<const f32x4*>(d.bias + (cok ? ncol : 0));
+    if constexpr (EpiPre<MT, NT, FORM>::OPT) {
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+            for (int it = 0; it < G::IT; ++it) {
+                const int m = m0 + (wm * MT + i) * 32 + it * G::RPI + sr;
+                const bool ok = m < p.M && cok;   // out of range: element 0 of the tensor, as the generic form reads
+                if constexpr (FORM == ALDM_EPI_FORM_RES)
+                    q.opt[i][it] = *reinterpret_cast<const f32x4*>(d.res + (ok ? (int64_t)m * d.ldo + ncol : 0));
+                else
+                    q.opt[i][it] = *reinterpret_cast<const f32x4*>(d.rowbias + (ok ? (m / p.OHW) * p.rb_ld + ncol : 0));
+            }
+    }
+}
+
+// NP: parts of the bf16 images (operand and output: the host sends other output formats to the generic form)
+template <int MT, int NT, int NP, int FORM, int PAD = 4>
+__device__ __forceinline__ void igemm_epilogue_form(const IgemmK& p, f32x16 (&acc)[MT][NT], const EpiPre<MT, NT, FORM>& q, float* lds,
+                                                    int m0, int n0, int wave, int wm, int wn, int lane) {
+    using G = EpiGeom<NT>;
+    const aldm_igemm_desc& d = p.d;
+    const bool epi_st = (ALDM_DMA_ABLATE & 64) ? p.M == -12345 : true;   // (ablation builds: compute, never store)
+    constexpr int SP = NT * 32 + PAD;
+    constexpr int ITC = G::IT < 4 ? G::IT : 4;
+    const int l31 = lane & 31;
+    const int lh = lane >> 5;
+    float* stg = lds + wave * (32 * SP);
+    const int sr = lane / G::C4;
+    const int sc = (lane % G::C4) * 4;
+    const int ncol = n0 + wn * NT * 32 + sc;
+    float* const outp = d.out;
+    void* const simg = d.out_split;
+    const bool lrelu_img = d.out_split_act == ALDM_ACT_LRELU;
+    // The prefetched quads landed long ago, but the compiler's counter model only knows that they are older than whatever is in
+    // flight: pin them here, in front of the first store — a store counts in vmcnt like a load, and reading slab 1's quads after
+    // slab 0's stores would otherwise wait for those stores to be acknowledged.
+    asm volatile("" ::"v"(q.bias4));
+    if constexpr (EpiPre<MT, NT, FORM>::OPT) {
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+            for (int it = 0; it < G::IT; ++it) asm volatile("" ::"v"(q.opt[i][it]));
+    }
+#pragma unroll
+    for (int i = 0; i < MT; ++i) {
+        // registers -> LDS (wave private, conflict free: 32 consecutive columns per half wave)
+#pragma unroll
+        for (int j = 0; j < NT; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e)
+                stg[((e & 3) + 8 * (e >> 2) + 4 * lh) * SP + j * 32 + l31] = acc[i][j][e];
+#pragma unroll
+        for (int itc = 0; itc < G::IT; itc += ITC) {
+            f32x4 v[ITC];
+            int64_t rowoff[ITC];
+            unsigned okmask = 0;
+#pragma unroll
+            for (int it = 0; it < ITC; ++it) {
+                const int r = (itc + it) * G::RPI + sr;
+                v[it] = *reinterpret_cast<const f32x4*>(&stg[r * SP + sc]);
+                const int m = m0 + (wm * MT + i) * 32 + r;
+                const bool ok = m < p.M && ncol < d.N;
+                rowoff[it] = m;
+                okmask |= ((ok && epi_st) ? 1u : 0u) << it;
+            }
+#pragma unroll
+            for (int it = 0; it < ITC; ++it) {
+                v[it] += q.bias4;
+                if constexpr (EpiPre<MT, NT, FORM>::OPT) v[it] += q.opt[i][itc + it];
+            }
+            if (outp) {
+#pragma unroll
+                for (int it = 0; it < ITC; ++it)
+                    if ((okmask >> it) & 1u) *reinterpret_cast<f32x4*>(outp + rowoff[it] * d.ldo + ncol) = v[it];
+            }
+            if (simg) {
+                if (lrelu_img) {
+#pragma unroll
+                    for (int it = 0; it < ITC; ++it)
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) v[it][c] = v[it][c] > 0.0f ? v[it][c] : v[it][c] * d.out_split_slope;
+                }
+#pragma unroll
+                for (int it = 0; it < ITC; ++it)
+                    if ((okmask >> it) & 1u) split_store4_t<NP>(simg, rowoff[it], d.out_split_c, ncol, v[it]);
+            }
+        }
     }
 }
 

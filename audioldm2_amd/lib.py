@@ -11,13 +11,14 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ALDM_LIB_PATH") or os.path.join(_HERE, "libaldm_hip.so")  # override: debug builds
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 ACT_NONE, ACT_SILU, ACT_LRELU, ACT_TANH, ACT_LOGCLAMP, ACT_GELU, ACT_GELU_TANH = range(7)
 B_PACKED, B_NT = 0, 1
 EPI_PLAIN, EPI_GEGLU, EPI_QKV = 0, 1, 2
 GN_CHUNKED, GN_FUSED, GN_FUSED_SPLIT = 0, 1, 2
 FMT_BF16, FMT_F16 = 0, 1
+EPI_FORM_GENERIC, EPI_FORM_PLAIN, EPI_FORM_ROWBIAS, EPI_FORM_RES = range(4)
 
 
 class IgemmDesc(C.Structure):
@@ -64,6 +65,8 @@ _SIGS = {
                                   C.POINTER(C.c_int)]),
     "aldm_igemm_ws_floats": (C.c_int64, [C.POINTER(IgemmDesc)]),
     "aldm_igemm_plan_stages": (C.c_int, [C.POINTER(IgemmDesc)]),
+    "aldm_igemm_plan_epilogue": (C.c_int, [C.POINTER(IgemmDesc)]),
+    "aldm_igemm_epilogue_forms": (C.c_int, [C.c_int]),
     "aldm_igemm_force": (None, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "aldm_igemm_force_stages": (None, [C.c_int]),
     "aldm_igemm_wave8_mask": (C.c_int, [C.c_int]),

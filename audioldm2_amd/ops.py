@@ -546,6 +546,13 @@ def igemm_force(bm: int = 0, bn: int = 0, splits: int = 0, kgroups: int = 0, sta
     _l.load().aldm_igemm_force_stages(stages)
 
 
+def igemm_epilogue_forms(on: int = -1) -> int:
+    """Process-wide switch of the DMA-fed kernels' compile-time epilogue forms (aldm_igemm_epilogue_forms): 0 sends every launch
+    to the generic run-time epilogue, 1 enables the forms, anything else restores the default (on, or $ALDM_EPI_FORMS=0).  Results
+    are bitwise the same either way.  Returns the previous setting (0 / 1)."""
+    return _l.load().aldm_igemm_epilogue_forms(on)
+
+
 def attention_mma(mode: int) -> int:
     """Matrix-core path of ops.attention (aldm_attention_mma): 1 fp32 MFMA, 2 bf16-split, -1 default.  Returns the
     previous mode."""

@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 /* ---- library / error ------------------------------------------------------------------ */
-int aldm_version(void);              /* ABI version (16), bumped on any struct / entry change */
+int aldm_version(void);              /* ABI version (17), bumped on any struct / entry change */
 const char* aldm_last_error(void);   /* message of the last failing call on this thread     */
 
 /* ---- activations usable as prologue (applied to the gathered input) or epilogue -------- */
@@ -212,6 +212,20 @@ int aldm_igemm_plan(const aldm_igemm_desc* d, int* bm, int* bn, int64_t* flops, 
 /* Host-only query: LDS ring depth of the DMA-fed kernel this descriptor launches (a_split set), 0 for the register-
  * staged kernels, negative on an invalid descriptor.                                                            */
 int aldm_igemm_plan_stages(const aldm_igemm_desc* d);
+/* ABI v17: compile-time epilogue forms of the DMA-fed kernels (csrc/igemm_epilogue.h).  A launch with the plain epilogue, no
+ * split-K, no activation, alpha == 1, no accumulate, no row remap, N % 4 == 0 and 16-byte aligned / float4-pitched out, res, bias
+ * and rowbias, whose split-image output (if any) has the operand's bf16 format, on a kernel instantiation that has the forms (the
+ * classic and loader-wave kernels' 64x64 / 64x128 / 128x64 tiles and the halo-patch kernel's 128x128 tile, 3-part bf16 images),
+ * runs a straight-line epilogue whose bias / residual / row-bias quads are fetched before the K loop: PLAIN (bias or nothing),
+ * ROWBIAS, RES.  A launch with both a residual and a row bias, and every other launch, runs the GENERIC run-time epilogue.
+ * Results are bit for bit the same either way.                                                                              */
+enum { ALDM_EPI_FORM_GENERIC = 0, ALDM_EPI_FORM_PLAIN = 1, ALDM_EPI_FORM_ROWBIAS = 2, ALDM_EPI_FORM_RES = 3 };
+/* Host-only query: the ALDM_EPI_FORM_* aldm_igemm would run this descriptor's epilogue in (under the current force / switch
+ * settings), negative on an invalid descriptor.                                                                          */
+int aldm_igemm_plan_epilogue(const aldm_igemm_desc* d);
+/* Process-wide switch (tests / A-B runs): on = 0 sends every launch to the generic epilogue, on = 1 enables the forms, any other
+ * value restores the default (on, or $ALDM_EPI_FORMS=0: off).  Returns the value that was in force (0 / 1).                  */
+int aldm_igemm_epilogue_forms(int on);
 /* Tuning override (tests / tools): force the block tile and split-K factor of subsequent
  * aldm_igemm calls on this thread; bm = 0 => automatic.  bm x bn in {128x128,128x64,64x128,64x64,128x32}. */
 void aldm_igemm_force(int bm, int bn, int splits, int kgroups);

@@ -22,7 +22,9 @@ def collect(root, counter):
                 m = re.search(r"igemm(?:_dma(?:_lw|_ws|_os)?)?_kernel<[^>]*>", r["Kernel_Name"])
                 if not m:
                     continue
-                a = acc[m.group(0)]
+                # the classic and loader-wave kernels end in their epilogue form (csrc/igemm_epilogue.h): one record per tile, over
+                # all its forms — the key bench.py looks an instantiation up under
+                a = acc[re.sub(r"(true|false), \d+>$", r"\1>", m.group(0))]
                 a[0] += 1
                 a[1] += float(r["Counter_Value"])
     return acc
@@ -34,7 +36,7 @@ def main():
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from audioldm2_amd.lib import source_hash, tuning_hash
     out = {"source_hash": source_hash(), "igemm_source_hash": source_hash("igemm"), "tuning_hash": tuning_hash(),
-           "source": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (two runs) of " +
+           "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (two counters-only runs) of " +
                      (sys.argv[4] if len(sys.argv) > 4 else
                       "ALDM_NO_GRAPH=1 python bench.py --full --steps 1 --warmup 0 --ddim-steps 2 --no-cpu-baseline"),
            "units": "bytes per launch, averaged over all launches of the instantiation in that command (all prologue modes)",
