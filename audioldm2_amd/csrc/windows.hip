@@ -1,0 +1,139 @@
+// windows.hip — the two per-step launches of windowed (long-form) diffusion: the window gather in front of the UNet pass and the
+// tapered, normalised overlap-add behind it.  Both are HBM-bound copies with at most `cover` multiply-adds per
+// element: 16-byte accesses along the contiguous F axis where F % 4 == 0 and the pointers are aligned, a scalar path otherwise,
+// grid-stride, 64-bit indexing, fp32.  The window starts travel as a kernel argument (aldm_window_starts, by value): a captured
+// step graph carries them, there is no device table and no copy inside a capture; every index into them is wave-uniform.
+#include "common.h"
+
+namespace aldm {
+
+static inline int win_blocks(int64_t n) {
+    int64_t b = cdiv64(n, 256);
+    if (b > 8192) b = 8192;
+    if (b < 1) b = 1;
+    return (int)b;
+}
+
+template <int V> struct vec_of;
+template <> struct vec_of<4> { typedef f32x4 type; };
+template <> struct vec_of<1> { typedef float type; };
+
+// win[(j*B + b), c, p, f] = x[b, c, s_j + p, f].  blockIdx.y = j; per (b, c) the Tw*F floats are contiguous on both sides.
+// per_row = Tw*F / V units per (b, c); total = B*C*per_row units per window.
+template <int V>
+__global__ void window_gather_kernel(const float* __restrict__ x, float* __restrict__ win, aldm_window_starts st, int T, int F,
+                                     int64_t per_row, int64_t total) {
+    typedef typename vec_of<V>::type vec;
+    const int j = blockIdx.y;
+    const int64_t src0 = (int64_t)st.s[j] * F;          // the window's offset inside a (b, c) plane of x
+    const int64_t plane = (int64_t)T * F;
+    float* dst = win + (int64_t)j * total * V;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t bc = i / per_row, off = i - bc * per_row;
+        *reinterpret_cast<vec*>(dst + i * V) = *reinterpret_cast<const vec*>(x + bc * plane + src0 + off * V);
+    }
+}
+
+// out[h, b, c, t, f] = sum over the windows j that cover t, ascending j, of wn[j, t - s_j] * win[h, j*B + b, c, t - s_j, f]: the
+// first term a plain multiply, every later one a fused multiply-add.  Gather form: one thread owns an output element (V of them
+// along F), so there are no atomics and the result does not depend on the launch geometry.  total = H*B*C*T*(F/V) units.
+template <int V>
+__global__ void window_merge_kernel(const float* __restrict__ win, const float* __restrict__ wn, float* __restrict__ out,
+                                    aldm_window_starts st, int B, int W, int C, int T, int Tw, int F, int64_t total) {
+    typedef typename vec_of<V>::type vec;
+    const int FV = F / V;
+    const int64_t wplane = (int64_t)Tw * F;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        int64_t q = i / FV;
+        const int fv = (int)(i - q * FV);
+        const int t = (int)(q % T);
+        q /= T;
+        const int c = (int)(q % C);
+        q /= C;
+        const int b = (int)(q % B);
+        const int64_t h = q / B;
+        vec acc = vec(0.0f);
+        bool first = true;
+        for (int j = 0; j < W; ++j) {
+            const int p = t - st.s[j];
+            if (p < 0 || p >= Tw) continue;
+            const float wv = wn[(int64_t)j * Tw + p];
+            const vec e = *reinterpret_cast<const vec*>(win + ((((h * W + j) * B + b) * C + c) * wplane + (int64_t)p * F + fv * V));
+            if (first) {
+                acc = wv * e;
+                first = false;
+            } else if constexpr (V == 4) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) acc[k] = __builtin_fmaf(wv, e[k], acc[k]);
+            } else {
+                acc = __builtin_fmaf(wv, e, acc);
+            }
+        }
+        *reinterpret_cast<vec*>(out + i * V) = acc;
+    }
+}
+
+// the host-side checks both entries share: the shape, and starts that tile [0, T) with windows of Tw
+static int window_args_ok(const char* name, const aldm_window_starts& st, int B, int W, int C, int T, int Tw, int F) {
+    ALDM_CHECK(B > 0 && C > 0 && F > 0 && Tw > 0 && T >= Tw, "%s: bad shape (B=%d, C=%d, T=%d, Tw=%d, F=%d)", name, B, C, T, Tw, F);
+    ALDM_CHECK(W >= 1 && W <= ALDM_MAX_WINDOWS && st.n == W, "%s: W=%d windows with %d starts (1 <= W == n <= %d)", name, W, st.n,
+               ALDM_MAX_WINDOWS);
+    ALDM_CHECK(st.s[0] == 0, "%s: starts[0]=%d must be 0", name, st.s[0]);
+    for (int j = 1; j < W; ++j) {
+        ALDM_CHECK(st.s[j] > st.s[j - 1], "%s: starts must ascend (starts[%d]=%d after %d)", name, j, st.s[j], st.s[j - 1]);
+        ALDM_CHECK(st.s[j] - st.s[j - 1] <= Tw, "%s: gap of %d frames between starts[%d] and starts[%d] exceeds Tw=%d: frames "
+                   "without a window", name, st.s[j] - st.s[j - 1], j - 1, j, Tw);
+    }
+    ALDM_CHECK(st.s[W - 1] == T - Tw, "%s: the last start %d must be T - Tw = %d", name, st.s[W - 1], T - Tw);
+    ALDM_CHECK((int64_t)W * B * C * Tw * F <= (1ll << 40), "%s: %lld window elements", name, (long long)W * B * C * Tw * F);
+    return 0;
+}
+
+static inline bool spans_overlap(const float* a, int64_t na, const float* b, int64_t nb) {
+    return (uintptr_t)a < (uintptr_t)(b + nb) && (uintptr_t)b < (uintptr_t)(a + na);
+}
+
+}  // namespace aldm
+
+using namespace aldm;
+
+extern "C" int aldm_window_gather(const float* x, float* win, aldm_window_starts starts, int B, int W, int C, int T, int Tw, int F,
+                                  void* stream) {
+    ALDM_CHECK(x && win, "aldm_window_gather: null pointer");
+    if (window_args_ok("aldm_window_gather", starts, B, W, C, T, Tw, F) != 0) return -1;
+    const int64_t n_x = (int64_t)B * C * T * F, n_w = (int64_t)W * B * C * Tw * F;
+    ALDM_CHECK(!spans_overlap(x, n_x, win, n_w), "aldm_window_gather: win overlaps x");
+    const int64_t per_window = (int64_t)B * C * Tw * F;
+    const dim3 block(256);
+    if (F % 4 == 0 && (((uintptr_t)x | (uintptr_t)win) & 15) == 0) {
+        const dim3 grid(win_blocks(per_window / 4), W);
+        hipLaunchKernelGGL(window_gather_kernel<4>, grid, block, 0, (hipStream_t)stream, x, win, starts, T, F,
+                           (int64_t)Tw * F / 4, per_window / 4);
+    } else {
+        const dim3 grid(win_blocks(per_window), W);
+        hipLaunchKernelGGL(window_gather_kernel<1>, grid, block, 0, (hipStream_t)stream, x, win, starts, T, F, (int64_t)Tw * F,
+                           per_window);
+    }
+    ALDM_LAUNCH_CHECK("aldm_window_gather");
+    return 0;
+}
+
+extern "C" int aldm_window_merge(const float* win, const float* wn, float* out, aldm_window_starts starts, int H, int B, int W, int C,
+                                 int T, int Tw, int F, void* stream) {
+    ALDM_CHECK(win && wn && out, "aldm_window_merge: null pointer");
+    ALDM_CHECK(H == 1 || H == 2, "aldm_window_merge: H=%d: 1, or 2 for the [uncond ; cond] pair", H);
+    if (window_args_ok("aldm_window_merge", starts, B, W, C, T, Tw, F) != 0) return -1;
+    const int64_t n_out = (int64_t)H * B * C * T * F, n_w = (int64_t)H * W * B * C * Tw * F;
+    ALDM_CHECK(!spans_overlap(out, n_out, win, n_w) && !spans_overlap(out, n_out, wn, (int64_t)W * Tw),
+               "aldm_window_merge: out overlaps win or wn");
+    const dim3 block(256);
+    if (F % 4 == 0 && (((uintptr_t)win | (uintptr_t)out) & 15) == 0) {
+        hipLaunchKernelGGL(window_merge_kernel<4>, dim3(win_blocks(n_out / 4)), block, 0, (hipStream_t)stream, win, wn, out, starts, B,
+                           W, C, T, Tw, F, n_out / 4);
+    } else {
+        hipLaunchKernelGGL(window_merge_kernel<1>, dim3(win_blocks(n_out)), block, 0, (hipStream_t)stream, win, wn, out, starts, B, W,
+                           C, T, Tw, F, n_out);
+    }
+    ALDM_LAUNCH_CHECK("aldm_window_merge");
+    return 0;
+}

@@ -80,9 +80,10 @@ class DDIMSampler(SamplerBase):
                img_callback=None, quantize_x0=False, eta=0.0, mask=None, x0=None, temperature=1.0,
                noise_dropout=0.0, score_corrector=None, corrector_kwargs=None, verbose=True, x_T=None,
                log_every_t=100, unconditional_guidance_scale=1.0, unconditional_conditioning=None,
-               dynamic_threshold=None, ucg_schedule=None, guidance_rescale=0.0, t_start=None, **kwargs):
-        """ddim.py:94-163, plus `guidance_rescale` (phi of Lin et al. 2023; 0: off — the reference's step) and `t_start` (None: the
-        whole schedule; k: its first k entries, indices k-1 ... 0, from x_T — see check_t_start)"""
+               dynamic_threshold=None, ucg_schedule=None, guidance_rescale=0.0, t_start=None, windows=None, **kwargs):
+        """ddim.py:94-163, plus `guidance_rescale` (phi of Lin et al. 2023; 0: off — the reference's step), `t_start` (None: the
+        whole schedule; k: its first k entries, indices k-1 ... 0, from x_T — see check_t_start) and `windows` (None, or a
+        windows.window_plan over the long latent `shape`: windowed diffusion, see SamplerBase.plan_run)"""
         guidance_rescale = check_guidance_rescale(guidance_rescale)
         if quantize_x0 or score_corrector is not None or dynamic_threshold is not None \
                 or noise_dropout != 0.0 or ucg_schedule is not None:
@@ -96,7 +97,7 @@ class DDIMSampler(SamplerBase):
                                   log_every_t=log_every_t,
                                   unconditional_guidance_scale=unconditional_guidance_scale,
                                   unconditional_conditioning=unconditional_conditioning, guidance_rescale=guidance_rescale,
-                                  t_start=t_start)
+                                  t_start=t_start, windows=windows)
 
     # ------------------------------------------------------------------------------------------
     def _draw_noise(self, shape, steps, x_T, with_mask):
@@ -118,8 +119,9 @@ class DDIMSampler(SamplerBase):
                       log_every_t=100, temperature=1.0, noise_dropout=0.0, score_corrector=None,
                       corrector_kwargs=None, unconditional_guidance_scale=1.0,
                       unconditional_conditioning=None, dynamic_threshold=None, ucg_schedule=None, guidance_rescale=0.0,
-                      t_start=None):
-        """ddim.py:166-262; `t_start=k`: run exactly the schedule's first k entries (check_t_start)"""
+                      t_start=None, windows=None):
+        """ddim.py:166-262; `t_start=k`: run exactly the schedule's first k entries (check_t_start); `windows`: a window plan
+        over the long latent `shape` (SamplerBase.plan_run) — gather and merge become two nodes of the step graph"""
         guidance_rescale = check_guidance_rescale(guidance_rescale)
         if ddim_use_original_steps:
             # the reference's own p_sample_ddim reads `self.model.ddim_sigmas_for_original_num_steps` here (ddim.py:324-327), a
@@ -135,8 +137,9 @@ class DDIMSampler(SamplerBase):
         plan = self.plan_run(cond, shape, x_T, t_start, timesteps,
                              lambda n, cfg: guidance_table(self.ddim_coef[:n].flip(0), unconditional_guidance_scale, cfg,
                                                            guidance_rescale),
-                             unconditional_guidance_scale, unconditional_conditioning, guidance_rescale, mask, x0)
+                             unconditional_guidance_scale, unconditional_conditioning, guidance_rescale, mask, x0, windows)
         total_steps, use_cfg, rescale, img, prepared = plan.total_steps, plan.use_cfg, plan.rescale, plan.img, plan.prepared
+        cond, unconditional_conditioning = plan.cond, plan.uncond   # tiled W times in a windowed run, else the arguments
         intermediates = {"x_inter": [img], "pred_x0": [img]}
         if total_steps == 0:
             return img, intermediates
@@ -158,6 +161,10 @@ class DDIMSampler(SamplerBase):
             # `rescale`: the launch sequence differs; the VALUES of the scale and phi live in coef_all, copied in below
             key = (shape, total_steps, tuple(tuple(c.shape) for c in prepared["ctxs"]),
                    None if prepared["y"] is None else tuple(prepared["y"].shape), rescale)
+            if windows is not None:
+                # the starts are kernel arguments of the captured gather and merge nodes
+                from .windows import plan_key
+                key = key + (plan_key(windows),)
         ent = unet._graph_cache.get(key) if can_cache else None
         if ent is not None and ent.get("kv") is None:
             # the entry never got as far as recording the K/V buffers its graph reads (e.g. an interrupted first run)
@@ -181,10 +188,13 @@ class DDIMSampler(SamplerBase):
                    "noise_all": torch.empty((total_steps,) + shape, device=dev, dtype=torch.float32), "prepared": prepared}
             if rescale:
                 ent["eps_g"] = torch.empty_like(img)   # the rescaled combined model output
+            if plan.win is not None:
+                ent["win"] = plan.win   # the window plan and the static buffers of the gather and the merge
 
             def step(e=ent):
                 x_c = e["x_cur"]
-                eps = self.model_output(x_c, e["t_cur"], b, cond, unconditional_conditioning, use_cfg, e["prepared"])
+                eps = self.model_output(x_c, e["t_cur"], b, cond, unconditional_conditioning, use_cfg, e["prepared"],
+                                        win=e.get("win"))
                 if rescale:
                     eps = ops.cfg_rescale_indexed(eps, e["eps_g"], e["coef_all"], e["step_idx"])
                 ops.ddim_step_indexed(x_c, eps, e["noise_all"], e["coef_all"], e["step_idx"], e["pred_x0"])

@@ -67,6 +67,7 @@ class DPMSolverSampler(SamplerBase):
         # carries: `sample` sets it on every call from its `guidance_rescale=` keyword (absent: 0), `dpm_sampling` reads it.
         self.guidance_rescale = 0.0
         self.t_start = None   # the same way: `sample` sets it from its `t_start=` keyword (absent: None), `dpm_sampling` reads it
+        self.windows = None   # the same way: a windows.window_plan over the long latent (`windows=`), or None
 
     def make_schedule(self, ddim_num_steps, ddim_discretize="uniform", ddim_eta=0.0, verbose=True):
         """DDIM's timestep grid and abar tables at eta = 0 (host side), and the solver's coefficient table for the whole grid."""
@@ -94,6 +95,7 @@ class DPMSolverSampler(SamplerBase):
         # `t_start` (None or absent: the whole schedule; k: its first k entries, indices k-1 ... 0, from x_T) is read from **kwargs
         # like `guidance_rescale`, and becomes `self.t_start` for this run
         self.t_start = check_t_start(kwargs.pop("t_start", None), kwargs.get("timesteps"), len(self.ddim_timesteps))
+        self.windows = kwargs.pop("windows", None)   # the same way: windowed diffusion over the long `shape` (SamplerBase.plan_run)
         C, H, W = shape
         size = (batch_size, C, H, W)
         return self.dpm_sampling(conditioning, size, callback=callback, img_callback=img_callback,
@@ -109,7 +111,8 @@ class DPMSolverSampler(SamplerBase):
                      quantize_denoised=False, mask=None, x0=None, img_callback=None, log_every_t=100, temperature=1.0,
                      noise_dropout=0.0, score_corrector=None, corrector_kwargs=None, unconditional_guidance_scale=1.0,
                      unconditional_conditioning=None):
-        """PLMSSampler.plms_sampling's parameter list and loop structure; guidance rescale: `self.guidance_rescale`."""
+        """PLMSSampler.plms_sampling's parameter list and loop structure; guidance rescale: `self.guidance_rescale`; a window plan over
+        the long `shape`: `self.windows`."""
         guidance_rescale = check_guidance_rescale(self.guidance_rescale)
         self._refuse(ddim_use_original_steps, quantize_denoised, score_corrector, noise_dropout)
         dev = torch.device("cuda")
@@ -120,8 +123,9 @@ class DPMSolverSampler(SamplerBase):
         plan = self.plan_run(cond, shape, x_T, self.t_start, timesteps,
                              lambda n, cfg: guidance_table(self.dpm_coef if n == self.dpm_coef.shape[0] else self._table(n),
                                                            unconditional_guidance_scale, cfg, guidance_rescale),
-                             unconditional_guidance_scale, unconditional_conditioning, guidance_rescale, mask, x0)
+                             unconditional_guidance_scale, unconditional_conditioning, guidance_rescale, mask, x0, self.windows)
         total_steps, use_cfg, rescale, draw, img = plan.total_steps, plan.use_cfg, plan.rescale, plan.draw, plan.img
+        cond, unconditional_conditioning = plan.cond, plan.uncond   # tiled W times in a windowed run, else the arguments
         intermediates = {"x_inter": [img], "pred_x0": [img]}
         if total_steps == 0:
             return img, intermediates
@@ -134,7 +138,7 @@ class DPMSolverSampler(SamplerBase):
         eps_g = torch.empty_like(img) if rescale else None   # the rescaled combined model output
 
         def step():
-            eps = self.model_output(x_cur, t_cur, b, cond, unconditional_conditioning, use_cfg, prepared)
+            eps = self.model_output(x_cur, t_cur, b, cond, unconditional_conditioning, use_cfg, prepared, win=plan.win)
             if rescale:
                 eps = ops.cfg_rescale_indexed(eps, eps_g, coef, step_idx)
             ops.dpmpp_step_indexed(x_cur, eps, pred_x0, coef, step_idx)

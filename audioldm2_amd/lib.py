@@ -11,7 +11,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ALDM_LIB_PATH") or os.path.join(_HERE, "libaldm_hip.so")  # override: debug builds
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 ACT_NONE, ACT_SILU, ACT_LRELU, ACT_TANH, ACT_LOGCLAMP, ACT_GELU, ACT_GELU_TANH = range(7)
 B_PACKED, B_NT = 0, 1
@@ -54,6 +54,15 @@ class IgemmDesc(C.Structure):
         ("a_fmt", C.c_int32), ("acc_scale", C.c_float), ("out_split_parts", C.c_int32),
         ("out_split_fmt", C.c_int32), ("out_split_scale", C.c_float), ("vt_scale", C.c_float),
     ]
+
+
+MAX_WINDOWS = 32
+
+
+class WindowStarts(C.Structure):
+    """Mirror of `struct aldm_window_starts` (include/aldm_hip.h), passed by value: the window starts of a long-form plan."""
+
+    _fields_ = [("n", C.c_int), ("s", C.c_int * MAX_WINDOWS)]
 
 
 _SIGS = {
@@ -175,6 +184,10 @@ _SIGS = {
                                      C.c_int64, C.c_void_p]),
     "aldm_posterior_qsample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                          C.c_int, C.c_int, C.c_int64, C.c_void_p]),
+    "aldm_window_gather": (C.c_int, [C.c_void_p, C.c_void_p, WindowStarts, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     C.c_void_p]),
+    "aldm_window_merge": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, WindowStarts, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                    C.c_int, C.c_int, C.c_void_p]),
     "aldm_axpby": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int64,
                              C.c_void_p]),
     "aldm_reflect_pad_1d": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,

@@ -1602,6 +1602,73 @@ def posterior_qsample(moments_cl: torch.Tensor, n_post: torch.Tensor, n_enc: tor
     return z, x_t
 
 
+def _window_starts(plan) -> "_l.WindowStarts":
+    """plan.starts as the by-value kernel argument (built once per plan)."""
+    st = getattr(plan, "_starts_arg", None)
+    if st is None:
+        if len(plan.starts) > _l.MAX_WINDOWS:
+            raise RuntimeError(f"window plan: {len(plan.starts)} windows, at most {_l.MAX_WINDOWS}")
+        st = _l.WindowStarts()
+        st.n = len(plan.starts)
+        for j, s in enumerate(plan.starts):
+            st.s[j] = int(s)
+        plan._starts_arg = st
+    return st
+
+
+def _no_overlap(out: torch.Tensor, what: str, others) -> None:
+    a0, a1 = out.data_ptr(), out.data_ptr() + 4 * out.numel()
+    for t, name in others:
+        b0, b1 = t.data_ptr(), t.data_ptr() + 4 * t.numel()
+        if a0 < b1 and b0 < a1:
+            raise RuntimeError(f"{what} overlaps {name}: the output must not alias an operand")
+
+
+def window_gather(x: torch.Tensor, plan, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The windows of a long tensor (aldm_window_gather): x [B, C, T, F] -> [W*B, C, Tw, F], row j*B + b = x[b, :, s_j:s_j + Tw]
+    (window-major), a bit-exact copy.  `plan`: windows.window_plan(T, Tw, hop); `out`: write into this (it may not overlap x)."""
+    _chk(x, "window_gather.x")
+    if x.dim() != 4 or x.shape[2] != plan.T or x.numel() == 0:
+        raise RuntimeError(f"window_gather: x must be [B, C, T={plan.T}, F], got {tuple(x.shape)}")
+    B, C, T, F = x.shape
+    shape = (plan.W * B, C, plan.Tw, F)
+    if out is None:
+        out = torch.empty(shape, device=x.device, dtype=torch.float32)
+    _chk(out, "window_gather.out")
+    if tuple(out.shape) != shape:
+        raise RuntimeError(f"window_gather.out: expected {shape}, got {tuple(out.shape)}")
+    _no_overlap(out, "window_gather.out", [(x, "x")])
+    _l.check(_l.load().aldm_window_gather(x.data_ptr(), out.data_ptr(), _window_starts(plan), B, plan.W, C, T, plan.Tw, F,
+                                          _stream()), "window_gather")
+    return out
+
+
+def window_merge(win: torch.Tensor, plan, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The tapered, normalised overlap-add of window-wise tensors (aldm_window_merge): win [W*B, C, Tw, F] -> [B, C, T, F], or
+    win [2, W*B, C, Tw, F] (the [uncond ; cond] pair of a guided UNet pass) -> [2, B, C, T, F]; rows window-major as
+    window_gather writes them.  Per output element the covering windows in ascending order, wn*e first, then one fmaf each, in
+    fp32: bitwise reproducible.  `out`: write into this (it may not overlap win)."""
+    from .windows import device_weights
+    _chk(win, "window_merge.win")
+    if win.dim() not in (4, 5) or (win.dim() == 5 and win.shape[0] != 2) or win.shape[-2] != plan.Tw or win.numel() == 0 \
+            or win.shape[-4] % plan.W != 0:
+        raise RuntimeError(f"window_merge: win must be [W*B, C, Tw, F] or [2, W*B, C, Tw, F] with W={plan.W}, Tw={plan.Tw}, got "
+                           f"{tuple(win.shape)}")
+    H = 2 if win.dim() == 5 else 1
+    B, C, F = win.shape[-4] // plan.W, win.shape[-3], win.shape[-1]
+    shape = ((2,) if win.dim() == 5 else ()) + (B, C, plan.T, F)
+    if out is None:
+        out = torch.empty(shape, device=win.device, dtype=torch.float32)
+    _chk(out, "window_merge.out")
+    if tuple(out.shape) != shape:
+        raise RuntimeError(f"window_merge.out: expected {shape}, got {tuple(out.shape)}")
+    wn = device_weights(plan, win.device)
+    _no_overlap(out, "window_merge.out", [(win, "win"), (wn, "wn")])
+    _l.check(_l.load().aldm_window_merge(win.data_ptr(), wn.data_ptr(), out.data_ptr(), _window_starts(plan), H, B, plan.W, C,
+                                         plan.T, plan.Tw, F, _stream()), "window_merge")
+    return out
+
+
 def axpby(a: torch.Tensor, b: Optional[torch.Tensor], alpha: float, beta: float = 0.0,
           out: Optional[torch.Tensor] = None) -> torch.Tensor:
     _chk(a, "axpby.a")

@@ -630,8 +630,21 @@ class LatentDiffusion(nn.Module):
             raise ValueError("t_start needs ddim_steps: the ancestral sampler has no such schedule")
         elif kwargs.get("x_T", None) is None:
             raise ValueError("t_start needs x_T: the latent the shortened run starts from")
+        # `windows` (a keyword of **kwargs: a windows.window_plan over a long latent, windowed diffusion) goes to whichever of the
+        # three samplers runs; the plan then sets the latent's length, the model's latent_t_size being the window
+        windows = kwargs.get("windows", None)
+        if windows is None:
+            kwargs.pop("windows", None)   # absent: today's call, unchanged
+        elif mask is not None or kwargs.get("x0", None) is not None:
+            raise ValueError("windows= together with mask / x0: inpainting over windows is not supported")
+        elif not (use_plms or sampler_name is not None or ddim):
+            raise ValueError("windows needs ddim_steps: the ancestral sampler has no windowed form")
+        elif windows.Tw != self.latent_t_size:
+            raise ValueError(f"windows: the plan's window is {windows.Tw} frames, the model's latent_t_size is {self.latent_t_size}")
         if mask is not None:
             shape = (self.channels, mask.size()[-2], mask.size()[-1])
+        elif windows is not None:
+            shape = (self.channels, windows.T, self.latent_f_size)
         elif t_start is not None:
             shape = tuple(kwargs["x_T"].shape[1:])
         else:
@@ -993,6 +1006,75 @@ class LatentDiffusion(nn.Module):
                                      **_sample_log_keywords(sampler, guidance_rescale, t_enc))
         return _waveform_of(self, samples, batch, text, n_gen, B0)
 
+    def long_form_plans(self, latent_t_size, hop=None):
+        """Pure host: (latent-domain plan, mel-domain plan) of a long clip of `latent_t_size` latent frames through windows of
+        `self.latent_t_size` frames, `hop` (default 3*Tw//4) apart — windows.window_plan; the mel plan is the latent one scaled by
+        the VAE's time factor.  ValueError for a length that is no multiple of 8 or shorter than the window, and for a bad hop."""
+        from .windows import window_plan
+        self.check_latent_t(latent_t_size)
+        Tw = self.latent_t_size
+        self.check_latent_t(Tw)
+        if latent_t_size < Tw:
+            raise ValueError(f"long-form generation: latent_t_size={latent_t_size} is shorter than the model's window of {Tw} "
+                             "frames: use generate_batch / text_to_audio for a clip of at most the trained length")
+        hop = 3 * Tw // 4 if hop is None else hop
+        f = 2 ** (self.first_stage_model.encoder.num_resolutions - 1)
+        return window_plan(int(latent_t_size), Tw, hop), window_plan(int(latent_t_size), Tw, hop, scale=f)
+
+    @torch.no_grad()
+    def generate_batch_long(self, batch, latent_t_size, hop=None, ddim_steps=200, ddim_eta=1.0, unconditional_guidance_scale=1.0,
+                            unconditional_conditioning=None, use_plms=False, sampler=None, negative_prompt=None,
+                            guidance_rescale=0.0, n_gen=1, shard=None):
+        """Long-form text-to-audio by windowed diffusion (MultiDiffusion, Bar-Tal et al. 2023): ONE long latent of
+        `latent_t_size` frames; at every step the UNet runs on overlapping windows of `self.latent_t_size` frames — the trained
+        length, `hop` frames apart (default 3*Tw//4) — in one pass over W*b rows, the windows' outputs are fused by a tapered,
+        normalised overlap-add (ops.window_gather / ops.window_merge, two nodes of the replayed step graph) and the sampler
+        steps the long latent.  The VAE decodes the final latent window by window, the mels are cross-faded by the same merge
+        kernel on the plan scaled to mel frames, and the vocoder runs once over the long mel.  UNet and VAE only ever see their
+        trained shape.  All windows share one conditioning: right for ambience, textures and music, wrong for a transcription
+        that should advance through the clip.  `sampler`, `negative_prompt` and `guidance_rescale` as in generate_batch.
+
+        Refused before any draw or GPU work: ddim_steps=None (the ancestral sampler has no windowed form), n_gen != 1 (the CLAP
+        re-ranker scores clips of the trained length), shard=, a length that is no multiple of 8 or shorter than the window, more
+        than 32 windows.
+
+        Host-generator order (RNG contract R): (R1) randn(B0, C, h, w) of the batch's mel, drawn and discarded
+        exactly as generate_batch does; (R1b) the rand(1) of _cfg_dropout_draw on every call but an object's first; the
+        conditioners' draws (twice with a negative prompt); randn(B0, C, latent_t_size, F), the long x_T; the sampler's per-step
+        draws at that long shape (DDIM one per step, PLMS one per step and one more in its first, DPM-Solver++ none)."""
+        if shard is not None:
+            raise ValueError("generate_batch_long: shard= is not supported on this path")
+        if ddim_steps is None:
+            raise ValueError("generate_batch_long needs ddim_steps: the ancestral sampler has no windowed form")
+        if n_gen != 1:
+            raise ValueError(f"generate_batch_long: n_gen must be 1, got {n_gen}: the CLAP re-ranker scores clips of the trained "
+                             "length, candidate re-ranking of long clips is not supported")
+        sampler = resolve_sampler(sampler, use_plms)
+        kw = {} if negative_prompt is None else {"negative_prompt": negative_prompt}
+        neg_batch, guidance_rescale = _guidance_kwargs(dict(kw, guidance_rescale=guidance_rescale), unconditional_guidance_scale,
+                                                       batch, ddim_steps)
+        plan, mel_plan = self.long_form_plans(latent_t_size, hop)
+        fb = batch["log_mel_spec"] if self.first_stage_key == "fbank" else batch[self.first_stage_key]
+        B0 = fb.shape[0]
+        f = 2 ** (self.first_stage_model.encoder.num_resolutions - 1)
+        torch.randn((B0, self.first_stage_model.embed_dim, fb.shape[-2] // f, fb.shape[-1] // f))  # (R1) draw & discard
+        self._cfg_dropout_draw()                                                                     # (R1b) every call but the first
+        c = self.get_learned_conditioning_dict(batch)
+        unconditional_conditioning = _unconditional_half(self, neg_batch, 1, B0, unconditional_guidance_scale,
+                                                         unconditional_conditioning)
+        samples, _ = self.sample_log(cond=c, batch_size=B0, x_T=None, ddim=True, ddim_steps=ddim_steps, eta=ddim_eta,
+                                     unconditional_guidance_scale=unconditional_guidance_scale,
+                                     unconditional_conditioning=unconditional_conditioning, use_plms=use_plms, windows=plan,
+                                     **_sample_log_keywords(sampler, guidance_rescale))
+        # the tail: the VAE at its trained shape on the W*B0 windows of the final latent, the mels cross-faded on the scaled plan
+        mel_w = self.decode_first_stage_cl(ops.window_gather(samples, plan))   # [W*B0, Tw*f, F_mel, 1] channels-last
+        mel = ops.window_merge(mel_w.view(mel_w.shape[0], 1, mel_w.shape[1], mel_w.shape[2]), mel_plan)   # [B0, 1, T*f, F_mel]
+        self.last_long_latent, self.last_long_mel = samples, mel
+        waveform = self.mel_spectrogram_to_waveform(mel, savepath="", bs=None, name=batch.get("fname"), save=False)
+        # a long clip has exactly one vocoder hop per mel frame: the few samples the vocoder's first transposed convolution
+        # appends (kernel 16 at stride 5: 32 of them at 16 kHz) are cut
+        return waveform[..., :mel.shape[-2] * int(np.prod(self.first_stage_model.vocoder.h.upsample_rates))]
+
 
 # ------------------------------------------------------------------------------------------------
 # The reference turns a transcription into an IPA string with phonemizer / espeak (`text2phoneme`, pipeline.py:33-34: a text
@@ -1242,6 +1324,27 @@ def text_to_audio(latent_diffusion, text, transcription="", seed=42, ddim_steps=
         return latent_diffusion.generate_batch(batch, unconditional_guidance_scale=guidance_scale,
                                                ddim_steps=ddim_steps, n_gen=n_candidate_gen_per_text,
                                                duration=duration, **sampler_kw)
+
+
+def text_to_audio_long(latent_diffusion, text, duration, overlap=2.5, transcription="", seed=42, ddim_steps=200, guidance_scale=3.5,
+                       sampler=None, negative_prompt=None, guidance_rescale=0.0):
+    """Long-form text-to-audio: a clip of `duration` seconds — longer than the model's trained length — by windowed diffusion
+    (LatentDiffusion.generate_batch_long): the UNet and the VAE work on windows of the model's `latent_t_size` frames that overlap
+    by `overlap` seconds, fused at every step.  latent_t_size = int(duration * latent_t_per_second) must be a multiple of 8 and
+    at least the window; hop = Tw - round(overlap * latent_t_per_second) must lie in [1, Tw]; both are refused before any GPU
+    work.  One candidate per prompt (no CLAP re-ranking of long clips); all windows share the prompt's conditioning, so a
+    transcription does not advance through the clip.  `sampler`, `negative_prompt`, `guidance_rescale` as in text_to_audio.  The
+    model's own latent_t_size is not changed.  Returns np.float32 [1, 1, samples]."""
+    sampler_kw = _sampler_kwargs(sampler, negative_prompt, guidance_rescale)
+    per_second = float(latent_diffusion.latent_t_per_second)
+    latent_t = int(duration * per_second)
+    hop = latent_diffusion.latent_t_size - int(round(overlap * per_second))
+    latent_diffusion.long_form_plans(latent_t, hop)   # refuse before any GPU work
+    seed_everything(int(seed))
+    batch = make_batch_for_text_to_audio(text, transcription=transcription, batchsize=1)
+    with torch.no_grad():
+        return latent_diffusion.generate_batch_long(batch, latent_t, hop=hop, unconditional_guidance_scale=guidance_scale,
+                                                    ddim_steps=ddim_steps, **sampler_kw)
 
 
 def audio_to_audio(latent_diffusion, text, original_audio_file_path, strength=0.5, transcription="", seed=42,

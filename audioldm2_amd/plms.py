@@ -41,6 +41,7 @@ class PLMSSampler(SamplerBase):
     def __init__(self, model, schedule="linear", **kwargs):
         super().__init__(model, schedule)
         self.t_start = None   # sampler state like guidance_rescale: `sample` sets it on every call, `plms_sampling` reads it
+        self.windows = None   # the same way: a windows.window_plan over the long latent (`windows=`), or None
         # phi of Lin et al. 2023 (section 3.4), 0: off.  Sampler state like the schedule, not a parameter: `plms_sampling` and
         # `p_sample_plms` keep the reference class's signatures, which have no **kwargs to take it.  `sample` sets it on every
         # call from its `guidance_rescale=` keyword (absent: 0); a caller of the two other methods sets the attribute.
@@ -67,6 +68,7 @@ class PLMSSampler(SamplerBase):
         # `t_start` (None or absent: the whole schedule; k: its first k entries, indices k-1 ... 0, from x_T) is read from **kwargs
         # like `guidance_rescale`, and becomes `self.t_start` for this run
         self.t_start = check_t_start(kwargs.pop("t_start", None), kwargs.get("timesteps"), len(self.ddim_timesteps))
+        self.windows = kwargs.pop("windows", None)   # the same way: windowed diffusion over the long `shape` (SamplerBase.plan_run)
         C, H, W = shape
         size = (batch_size, C, H, W)
         return self.plms_sampling(conditioning, size, callback=callback, img_callback=img_callback,
@@ -82,7 +84,7 @@ class PLMSSampler(SamplerBase):
                       quantize_denoised=False, mask=None, x0=None, img_callback=None, log_every_t=100, temperature=1.0,
                       noise_dropout=0.0, score_corrector=None, corrector_kwargs=None, unconditional_guidance_scale=1.0,
                       unconditional_conditioning=None):
-        """plms.py:156-258; guidance rescale: `self.guidance_rescale`"""
+        """plms.py:156-258; guidance rescale: `self.guidance_rescale`; a window plan over the long `shape`: `self.windows`"""
         guidance_rescale = check_guidance_rescale(self.guidance_rescale)
         self._refuse(ddim_use_original_steps, quantize_denoised, score_corrector, noise_dropout)
         dev = torch.device("cuda")
@@ -93,8 +95,9 @@ class PLMSSampler(SamplerBase):
         plan = self.plan_run(cond, shape, x_T, self.t_start, timesteps,
                              lambda n, cfg: guidance_table(self.plms_coef[:n].flip(0), unconditional_guidance_scale, cfg,
                                                            guidance_rescale),
-                             unconditional_guidance_scale, unconditional_conditioning, guidance_rescale, mask, x0)
+                             unconditional_guidance_scale, unconditional_conditioning, guidance_rescale, mask, x0, self.windows)
         total_steps, use_cfg, rescale, draw, img = plan.total_steps, plan.use_cfg, plan.rescale, plan.draw, plan.img
+        cond, unconditional_conditioning, win = plan.cond, plan.uncond, plan.win   # tiled W times in a windowed run
         intermediates = {"x_inter": [img], "pred_x0": [img]}
         if total_steps == 0:
             return img, intermediates
@@ -109,8 +112,10 @@ class PLMSSampler(SamplerBase):
 
         def guided_eps(x, t_row, out=None, idx=None):
             """eps [2, b, ...] for the step kernel to combine, or with rescale the combined and rescaled [b, ...] (row: the
-            counter's, or row 0 — the step's row in the eager calls of step 0)"""
-            eps = self.model_output(x, t_row, b, cond, unconditional_conditioning, use_cfg, prepared)
+            counter's, or row 0 — the step's row in the eager calls of step 0).  The eager calls (idx is None) keep their
+            results side by side: a windowed run merges them into fresh tensors, not the step graph's static one"""
+            eps = self.model_output(x, t_row, b, cond, unconditional_conditioning, use_cfg, prepared, win=win,
+                                    static=idx is not None)
             if not rescale:
                 return eps
             return ops.cfg_rescale_indexed(eps, torch.empty_like(img) if out is None else out, coef, idx)

@@ -3,7 +3,8 @@ run that is the same whichever update rule runs.
 
   * SamplerBase: the constructor, DDIM's timestep grid and abar tables (`make_schedule`), the run plan (`plan_run`: the cut of the
     schedule, the start latent, the device tables, the inpainting buffers, the batched guidance conditioning) and the UNet pass of
-    one step (`model_output`);
+    one step (`model_output`) — with a window plan (`windows=`, windows.py) the pass on the windows of a long latent
+    between a window gather and a window merge;
   * ddim_step_rows: the [S, 5] coefficient rows of DDIM's update with the reference's roundings (DDIM and PLMS), guidance_table:
     a sampler's [S, 8] table from its rows;
   * GraphStepper / drop_graph_entries: a fixed launch sequence run eagerly once, captured into a HIP graph, replayed;
@@ -22,6 +23,8 @@ from types import SimpleNamespace
 
 import numpy as np
 import torch
+
+from . import ops
 
 
 def make_ddim_timesteps(ddim_discr_method, num_ddim_timesteps, num_ddpm_timesteps, verbose=True):
@@ -376,11 +379,20 @@ class SamplerBase(object):
         if quantize_denoised or score_corrector is not None or noise_dropout != 0.0:
             raise NotImplementedError(f"{name}(HIP): option not used by the AudioLDM2 pipeline")
 
-    def model_output(self, x, t_row, b, cond, uncond, use_cfg, prepared):
+    def model_output(self, x, t_row, b, cond, uncond, use_cfg, prepared, win=None, static=True):
         """The UNet pass of one step: eps [2, b, ...] = [uncond ; cond] under guidance (combined inside the step kernel, or by
         ops.cfg_rescale_indexed), else eps [b, ...].  t_row: the step's timestep as floats, one entry per UNet row.  Guidance is ONE
         pass over 2b samples when the model has `apply_model_cfg` — asked at every call: it may be set on an instance — where the
-        reference runs two (ddim.py:293-296)."""
+        reference runs two (ddim.py:293-296).
+
+        `win` (plan_run's `p.win`, a windowed run): x is the long latent; its windows are gathered (ops.window_gather), the pass
+        above runs on the W*b window rows — cond, uncond, prepared and t_row are the W-fold tiled ones — and the window outputs
+        are merged back to the long shape (ops.window_merge): two launches around an unchanged pass.  `static`: gather and merge
+        into win's buffers (a step graph's static tensors); False: into fresh ones (eager calls whose results must coexist)."""
+        if win is not None:
+            xw = ops.window_gather(x, win.plan, out=win.xw if static else None)
+            eps_w = self.model_output(xw, t_row, win.plan.W * b, cond, uncond, use_cfg, prepared)
+            return ops.window_merge(eps_w.contiguous(), win.plan, out=win.merged if static else None)
         if not use_cfg:
             return self.model.apply_model(x, t_row[:b].long(), cond).contiguous()
         if hasattr(self.model, "apply_model_cfg"):
@@ -389,9 +401,15 @@ class SamplerBase(object):
         return torch.stack([self.model.apply_model(x, tl, uncond), self.model.apply_model(x, tl, cond)]).contiguous()
 
     def plan_run(self, cond, shape, x_T, t_start, timesteps, table, unconditional_guidance_scale, unconditional_conditioning,
-                 guidance_rescale, mask, x0):
+                 guidance_rescale, mask, x0, windows=None):
         """Everything a sampling loop needs before its first step, as one object.  `table(total_steps, use_cfg)` is the sampler's
         own [total_steps, 8] host coefficient table in loop order (i = 0 is the noisiest step, index = total_steps - 1).
+
+        `windows` (a latent-domain windows.window_plan, or None): a windowed run over the long `shape` [b, C, plan.T, F].  x_T and
+        the per-step noise keep the long shape; `p.cond` / `p.uncond` are the conditionings tiled W times (window-major), t_tab
+        has W times the columns, prepare_cfg sees the tiled pair, and `p.win` holds the plan and the two static window buffers
+        of model_output (xw [W*b, C, Tw, F], merged [2, b, ...] or [b, ...]).  Without a plan p.cond / p.uncond are the arguments
+        and p.win is None.  Not together with mask / x0.
 
         The cut of the schedule: `t_start=k` keeps exactly its first k entries, as `decode` cuts it (ddim.py:466-467; see
         check_t_start); `timesteps` keeps its first int(min(timesteps / S, 1) * S) - 1 entries (ddim.py:198-206).  `total_steps`
@@ -403,6 +421,13 @@ class SamplerBase(object):
         in this order: img, coef, t_tab, mask_d, x0_d, blend_coef, then the model's prepare_cfg."""
         dev = torch.device("cuda")
         shape = tuple(shape)
+        W = 1
+        if windows is not None:
+            if mask is not None or x0 is not None:
+                raise ValueError("windows= together with mask / x0: inpainting over windows is not supported")
+            if len(shape) != 4 or shape[2] != windows.T:
+                raise ValueError(f"windows= is a plan over T={windows.T} frames, the latent shape is {shape}")
+            W = windows.W
         ts = self.ddim_timesteps
         t_start = check_t_start(t_start, timesteps, ts.shape[0])
         if t_start is not None:
@@ -412,7 +437,8 @@ class SamplerBase(object):
             ts = ts[:subset_end]
         total_steps = ts.shape[0]
         use_cfg = not (unconditional_conditioning is None or unconditional_guidance_scale == 1.0)
-        p = SimpleNamespace(total_steps=total_steps, use_cfg=use_cfg, mask_d=None, x0_d=None, blend_coef=None, prepared=None)
+        p = SimpleNamespace(total_steps=total_steps, use_cfg=use_cfg, mask_d=None, x0_d=None, blend_coef=None, prepared=None,
+                            cond=cond, uncond=unconditional_conditioning, win=None)
         p.time_range = np.flip(ts).copy()   # own storage, positive strides: from_numpy refuses the flipped view, even of one entry
         # guidance rescale: the combine and the per-sample rescale run in a launch of their own in front of the step kernel
         p.rescale = use_cfg and guidance_rescale > 0.0
@@ -422,13 +448,19 @@ class SamplerBase(object):
             return p
         p.coef = table(total_steps, use_cfg).to(dev)
         tr = torch.from_numpy(p.time_range)
-        p.t_tab = tr.float()[:, None].repeat(1, (2 if use_cfg else 1) * shape[0]).to(dev).contiguous()
+        p.t_tab = tr.float()[:, None].repeat(1, (2 if use_cfg else 1) * W * shape[0]).to(dev).contiguous()
         if mask is not None:
             assert x0 is not None
             p.mask_d = mask.float().to(dev).expand(shape).contiguous()
             p.x0_d = x0.float().to(dev).contiguous()
             p.blend_coef = torch.stack([self.sqrt_alphas_cumprod[tr], self.sqrt_one_minus_alphas_cumprod[tr]],
                                        1).contiguous().to(dev)  # [S, 2] = {sqrt(abar_t), sqrt(1 - abar_t)}
+        if windows is not None:
+            from .windows import tile_cond
+            p.cond, p.uncond = tile_cond(cond, W), tile_cond(unconditional_conditioning, W)
+            b, C, _, F = shape
+            p.win = SimpleNamespace(plan=windows, xw=torch.empty((W * b, C, windows.Tw, F), device=dev, dtype=torch.float32),
+                                    merged=torch.empty(((2,) if use_cfg else ()) + shape, device=dev, dtype=torch.float32))
         if use_cfg and hasattr(self.model, "apply_model_cfg") and hasattr(self.model, "prepare_cfg"):
-            p.prepared = self.model.prepare_cfg(cond, unconditional_conditioning)
+            p.prepared = self.model.prepare_cfg(p.cond, p.uncond)
         return p

@@ -1,0 +1,100 @@
+"""Window plans of long-form generation (windowed diffusion: MultiDiffusion, Bar-Tal et al. 2023).  Pure host code.
+
+A long latent [b, C, T, F] is denoised through W overlapping windows of the UNet's trained length Tw along the time axis: at every
+step the windows are gathered (ops.window_gather), the UNet runs on the W*b window rows, and the window-wise outputs are fused by a
+tapered, normalised overlap-add (ops.window_merge) before the sampler's update of the long latent.  The plan is everything the two
+kernels need: the window starts and the normalised weights.
+"""
+from __future__ import annotations
+
+from types import SimpleNamespace
+
+import numpy as np
+import torch
+
+MAX_WINDOWS = 32   # the size of `aldm_window_starts` (include/aldm_hip.h): the starts travel as kernel arguments
+
+
+def _check_int(v, name):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+        raise ValueError(f"window_plan: {name} must be an integer, got {v!r}")
+    return int(v)
+
+
+def window_plan(T, Tw, hop, scale=1):
+    """The plan of windows of `Tw` frames, `hop` frames apart, over `T` frames -> an object with
+
+      starts  s_j = j*hop while s_j + Tw < T, then a final T - Tw: s_0 = 0, the last window ends at T, consecutive starts differ
+              by at most Tw; W = len(starts)
+      wn      [W, Tw] fp32, the normalised weights: the raw taper w[p] = min(1, (p+1)/(ramp+1), (Tw-p)/(ramp+1)), ramp = Tw - hop
+              (strictly positive), divided by the sum of the tapers of every window that covers the frame; fp64, rounded to
+              fp32 once.  Where one window covers a frame wn is exactly 1.0
+      cover   the largest number of windows over one frame
+      T, Tw, hop, W, scale   the numbers the plan was built from, after scaling
+
+    `scale` multiplies T, Tw and hop (and so the starts) first: the mel-domain plan of a latent-domain one (x4 for the 16 kHz VAE);
+    its taper is the same formula on the scaled numbers.
+
+    ValueError: T or Tw not a positive multiple of 8 (the UNet's three stride-2 levels), T < Tw, hop not an integer in [1, Tw],
+    more than 32 windows."""
+    T, Tw, hop, scale = _check_int(T, "T"), _check_int(Tw, "Tw"), _check_int(hop, "hop"), _check_int(scale, "scale")
+    for v, name in ((T, "T"), (Tw, "Tw")):
+        if v <= 0 or v % 8 != 0:
+            raise ValueError(f"window_plan: {name} must be a positive multiple of 8, got {v}")
+    if T < Tw:
+        raise ValueError(f"window_plan: T={T} is shorter than one window (Tw={Tw})")
+    if not 1 <= hop <= Tw:
+        raise ValueError(f"window_plan: hop must lie in [1, Tw={Tw}], got {hop}")
+    if scale < 1:
+        raise ValueError(f"window_plan: scale must be a positive integer, got {scale}")
+    T, Tw, hop = T * scale, Tw * scale, hop * scale
+    starts = []
+    s = 0
+    while s + Tw < T:
+        starts.append(s)
+        s += hop
+        if len(starts) >= MAX_WINDOWS:
+            raise ValueError(f"window_plan: T={T}, Tw={Tw}, hop={hop} needs more than {MAX_WINDOWS} windows")
+    starts.append(T - Tw)
+    W = len(starts)
+    ramp = Tw - hop
+    p = np.arange(Tw, dtype=np.float64)
+    w = np.minimum(1.0, np.minimum((p + 1.0) / (ramp + 1.0), (Tw - p) / (ramp + 1.0)))
+    norm = np.zeros(T, dtype=np.float64)
+    count = np.zeros(T, dtype=np.int64)
+    for s in starts:
+        norm[s:s + Tw] += w
+        count[s:s + Tw] += 1
+    wn = np.stack([w / norm[s:s + Tw] for s in starts])
+    # one window over a frame: w / w — exactly 1 in fp64 already; stated here because the kernels' bit-exact cases rest on it
+    assert all(np.all(wn[j][count[s:s + Tw] == 1] == 1.0) for j, s in enumerate(starts))
+    return SimpleNamespace(T=T, Tw=Tw, hop=hop, scale=scale, W=W, starts=tuple(starts), cover=int(count.max()),
+                           wn=torch.from_numpy(wn.astype(np.float32)).contiguous())
+
+
+def plan_key(plan):
+    """What identifies a plan's launch sequence (the starts are kernel arguments captured with a step graph)."""
+    return (plan.T, plan.Tw, tuple(plan.starts))
+
+
+def device_weights(plan, device):
+    """plan.wn on `device`, uploaded once per plan and device."""
+    cache = plan.__dict__.setdefault("_wn_dev", {})
+    key = str(device)
+    if key not in cache:
+        cache[key] = plan.wn.to(device).contiguous()
+    return cache[key]
+
+
+def tile_cond(c, W):
+    """A conditioning (a tensor, or lists / tuples / dicts of them, None passing through) repeated for W windows, window-major:
+    row j*b + i is sample i's — the order pipeline._tile_cond gives candidates, and ops.window_gather gives window rows."""
+    if c is None:
+        return None
+    if torch.is_tensor(c):
+        return torch.cat([c] * W, dim=0)
+    if isinstance(c, dict):
+        return {k: tile_cond(v, W) for k, v in c.items()}
+    if isinstance(c, (list, tuple)):
+        return type(c)(tile_cond(v, W) for v in c)
+    return c

@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 /* ---- library / error ------------------------------------------------------------------ */
-int aldm_version(void);              /* ABI version (17), bumped on any struct / entry change */
+int aldm_version(void);              /* ABI version (18), bumped on any struct / entry change */
 const char* aldm_last_error(void);   /* message of the last failing call on this thread     */
 
 /* ---- activations usable as prologue (applied to the gathered input) or epilogue -------- */
@@ -555,6 +555,28 @@ int aldm_inpaint_blend(const float* x0, const float* qnoise, const float* mask, 
  * the launch.                                                                                                                    */
 int aldm_posterior_qsample(const float* moments_cl, const float* n_post, const float* n_enc, const float* coef, float* z,
                            float* x_t, int B0, int n_gen, int C, int64_t hw, void* stream);
+/* Windowed (long-form) diffusion, ABI v18: a long latent [B, C, T, F] is denoised through W overlapping windows of
+ * Tw frames along T.  The window starts are passed BY VALUE, so a captured step graph carries them as kernel arguments: no device
+ * table, no copy inside a capture.  Both entries check them on the host before the launch: n == W <= ALDM_MAX_WINDOWS, s[0] == 0,
+ * strictly ascending with gaps <= Tw (every frame has a window), s[n-1] == T - Tw.                                               */
+#define ALDM_MAX_WINDOWS 32
+typedef struct aldm_window_starts {
+    int n;
+    int s[ALDM_MAX_WINDOWS];
+} aldm_window_starts;
+/* win[(j*B + b), c, p, f] = x[b, c, s_j + p, f]: x [B, C, T, F] -> win [W*B, C, Tw, F], window-major rows (the order in which a
+ * conditioning is tiled for W windows).  A bit-exact copy; win must not overlap x.                                             */
+int aldm_window_gather(const float* x, float* win, aldm_window_starts starts, int B, int W, int C, int T, int Tw, int F,
+                       void* stream);
+/* The tapered, normalised overlap-add of window-wise tensors: win [H, W*B, C, Tw, F], wn [W, Tw] (the normalised weights: over
+ * every frame they sum to 1) -> out [H, B, C, T, F]; H = 1, or 2 for the [uncond ; cond] pair of a guided UNet pass.
+ *   out[h, b, c, t, f] = sum over the windows j with s_j <= t < s_j + Tw, in ascending j, of wn[j, t - s_j] * win[h, j*B + b, c, t - s_j, f]
+ * in fp32: the first term a plain multiply, every later term one fmaf.  Gather form, no atomics: bitwise reproducible and
+ * independent of the launch geometry; a frame under one window with wn == 1 reproduces its input bit for bit; a non-finite input
+ * reaches exactly the frames its window covers.  out must overlap neither win nor wn.  The same entry cross-fades window-wise VAE
+ * decodes in the mel domain (C = 1, F = mel bins, the plan scaled by the VAE's time factor).                                    */
+int aldm_window_merge(const float* win, const float* wn, float* out, aldm_window_starts starts, int H, int B, int W, int C, int T,
+                      int Tw, int F, void* stream);
 /* generic y = alpha*a + beta*b (b may be NULL) */
 int aldm_axpby(const float* a, const float* b, float* y, float alpha, float beta, int64_t n,
                void* stream);
