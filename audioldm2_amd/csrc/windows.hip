@@ -1,5 +1,6 @@
-// windows.hip — the two per-step launches of windowed (long-form) diffusion: the window gather in front of the UNet pass and the
-// tapered, normalised overlap-add behind it.  Both are HBM-bound copies with at most `cover` multiply-adds per
+// windows.hip — the per-step launches of windowed (long-form) diffusion: the window gather in front of the UNet pass and the
+// tapered, normalised overlap-add behind it, and the gather fused with the inpainting blend of a kept source on
+// the long latent (§9f).  All are HBM-bound copies with at most `cover` multiply-adds (the blend: five operations) per
 // element: 16-byte accesses along the contiguous F axis where F % 4 == 0 and the pointers are aligned, a scalar path otherwise,
 // grid-stride, 64-bit indexing, fp32.  The window starts travel as a kernel argument (aldm_window_starts, by value): a captured
 // step graph carries them, there is no device table and no copy inside a capture; every index into them is wave-uniform.
@@ -73,7 +74,47 @@ __global__ void window_merge_kernel(const float* __restrict__ win, const float* 
     }
 }
 
-// the host-side checks both entries share: the shape, and starts that tile [0, T) with windows of Tw
+// The inpainting blend on the long latent and the window gather in one launch, scatter form (the mirror image of the merge): one
+// thread owns a long-latent element (V of them along F), reads x, x0, qnoise and mask once, writes the blended x back and then every
+// window copy of it — at most `cover` of them: win[(j*B + b), c, t - s_j, f] for the windows j with 0 <= t - s_j < Tw.  A window
+// position maps to one frame, so every element of win has exactly one writer, and the starts tile [0, T), so every element is
+// written: no atomics, independent of the launch geometry.  In place on x: the owner is its element's only reader and writer.  The
+// expression and its operation order are inpaint_blend_kernel's (elementwise.hip); built with -ffp-contract=off the launch is
+// bitwise that kernel followed by window_gather_kernel.  The q-noise and coefficient rows are selected by the device-side step
+// counter, each saturating at its table's last row (q_rows == 1: one staged draw per step).  total = B*C*T*(F/V) units.
+template <int V>
+__global__ void window_blend_gather_kernel(float* __restrict__ x, const float* __restrict__ x0, const float* __restrict__ qnoise,
+                                           const float* __restrict__ mask, const float* __restrict__ blend_coef,
+                                           const int* __restrict__ step_idx, int q_rows, int coef_rows, float* __restrict__ win,
+                                           aldm_window_starts st, int B, int W, int C, int T, int Tw, int F, int64_t total) {
+    typedef typename vec_of<V>::type vec;
+    int s = step_idx ? *step_idx : 0;
+    s = s < 0 ? 0 : s;
+    const int qr = s < q_rows ? s : q_rows - 1, cr = s < coef_rows ? s : coef_rows - 1;
+    const float sa = blend_coef[2 * cr], so = blend_coef[2 * cr + 1];
+    const float* qn = qnoise + (int64_t)qr * total * V;
+    const int FV = F / V;
+    const int64_t wplane = (int64_t)Tw * F;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        int64_t q = i / FV;
+        const int fv = (int)(i - q * FV);
+        const int t = (int)(q % T);
+        q /= T;
+        const int c = (int)(q % C);
+        const int64_t b = q / C;
+        const vec m = *reinterpret_cast<const vec*>(mask + i * V);
+        const vec orig = sa * *reinterpret_cast<const vec*>(x0 + i * V) + so * *reinterpret_cast<const vec*>(qn + i * V);
+        const vec v = orig * m + (1.0f - m) * *reinterpret_cast<const vec*>(x + i * V);
+        *reinterpret_cast<vec*>(x + i * V) = v;
+        for (int j = 0; j < W; ++j) {
+            const int p = t - st.s[j];
+            if (p < 0 || p >= Tw) continue;
+            *reinterpret_cast<vec*>(win + (((int64_t)j * B + b) * C + c) * wplane + (int64_t)p * F + fv * V) = v;
+        }
+    }
+}
+
+// the host-side checks the entries share: the shape, and starts that tile [0, T) with windows of Tw
 static int window_args_ok(const char* name, const aldm_window_starts& st, int B, int W, int C, int T, int Tw, int F) {
     ALDM_CHECK(B > 0 && C > 0 && F > 0 && Tw > 0 && T >= Tw, "%s: bad shape (B=%d, C=%d, T=%d, Tw=%d, F=%d)", name, B, C, T, Tw, F);
     ALDM_CHECK(W >= 1 && W <= ALDM_MAX_WINDOWS && st.n == W, "%s: W=%d windows with %d starts (1 <= W == n <= %d)", name, W, st.n,
@@ -115,6 +156,30 @@ extern "C" int aldm_window_gather(const float* x, float* win, aldm_window_starts
                            per_window);
     }
     ALDM_LAUNCH_CHECK("aldm_window_gather");
+    return 0;
+}
+
+extern "C" int aldm_window_blend_gather(float* x, const float* x0, const float* qnoise, const float* mask, const float* blend_coef,
+                                        const int* step_idx, int q_rows, int coef_rows, float* win, aldm_window_starts starts, int B,
+                                        int W, int C, int T, int Tw, int F, void* stream) {
+    ALDM_CHECK(x && x0 && qnoise && mask && blend_coef && win, "aldm_window_blend_gather: null pointer");
+    if (window_args_ok("aldm_window_blend_gather", starts, B, W, C, T, Tw, F) != 0) return -1;
+    ALDM_CHECK(q_rows >= 1 && coef_rows >= 1, "aldm_window_blend_gather: q_rows=%d and coef_rows=%d must be >= 1", q_rows, coef_rows);
+    const int64_t n_x = (int64_t)B * C * T * F, n_w = (int64_t)W * B * C * Tw * F, n_q = (int64_t)q_rows * n_x;
+    ALDM_CHECK(!spans_overlap(win, n_w, x, n_x) && !spans_overlap(win, n_w, x0, n_x) && !spans_overlap(win, n_w, qnoise, n_q) &&
+               !spans_overlap(win, n_w, mask, n_x), "aldm_window_blend_gather: win overlaps x, x0, qnoise or mask");
+    ALDM_CHECK(!spans_overlap(x, n_x, x0, n_x) && !spans_overlap(x, n_x, qnoise, n_q) && !spans_overlap(x, n_x, mask, n_x),
+               "aldm_window_blend_gather: x overlaps x0, qnoise or mask");
+    const dim3 block(256);
+    if (F % 4 == 0 &&
+        (((uintptr_t)x | (uintptr_t)x0 | (uintptr_t)qnoise | (uintptr_t)mask | (uintptr_t)win) & 15) == 0) {
+        hipLaunchKernelGGL(window_blend_gather_kernel<4>, dim3(win_blocks(n_x / 4)), block, 0, (hipStream_t)stream, x, x0, qnoise,
+                           mask, blend_coef, step_idx, q_rows, coef_rows, win, starts, B, W, C, T, Tw, F, n_x / 4);
+    } else {
+        hipLaunchKernelGGL(window_blend_gather_kernel<1>, dim3(win_blocks(n_x)), block, 0, (hipStream_t)stream, x, x0, qnoise, mask,
+                           blend_coef, step_idx, q_rows, coef_rows, win, starts, B, W, C, T, Tw, F, n_x);
+    }
+    ALDM_LAUNCH_CHECK("aldm_window_blend_gather");
     return 0;
 }
 

@@ -121,7 +121,9 @@ class DDIMSampler(SamplerBase):
                       unconditional_conditioning=None, dynamic_threshold=None, ucg_schedule=None, guidance_rescale=0.0,
                       t_start=None, windows=None):
         """ddim.py:166-262; `t_start=k`: run exactly the schedule's first k entries (check_t_start); `windows`: a window plan
-        over the long latent `shape` (SamplerBase.plan_run) — gather and merge become two nodes of the step graph"""
+        over the long latent `shape` (SamplerBase.plan_run) — gather and merge become two nodes of the step graph; a plan
+        with a source (windows.with_source) blends the source in inside the step: the gather node becomes ops.window_blend_gather,
+        which reads the feed's q-noise table with the graph's step counter — the host issues nothing new per step"""
         guidance_rescale = check_guidance_rescale(guidance_rescale)
         if ddim_use_original_steps:
             # the reference's own p_sample_ddim reads `self.model.ddim_sigmas_for_original_num_steps` here (ddim.py:324-327), a
@@ -154,7 +156,11 @@ class DDIMSampler(SamplerBase):
         # step's timestep row (aldm_step_advance) — between two replays the host issues nothing but a stream wait on the
         # noise upload event, once per 8 steps (round 2 issued three copies per step from the host).
         unet = getattr(getattr(self.model, "model", None), "diffusion_model", None)
-        can_cache = (prepared is not None and mask is None and self.use_graph and hasattr(unet, "refresh_context_kv")
+        # a window plan with a source: the blend is a node of the step graph (model_output), its q-noise the feed's table.  Like
+        # a masked run it stays out of the cross-run graph cache
+        blend = plan.win is not None and plan.win.blend
+        can_cache = (prepared is not None and mask is None and not blend and self.use_graph
+                     and hasattr(unet, "refresh_context_kv")
                      and os.environ.get("ALDM_NO_GRAPH_CACHE", "0") != "1")
         key = None
         if can_cache:
@@ -190,6 +196,10 @@ class DDIMSampler(SamplerBase):
                 ent["eps_g"] = torch.empty_like(img)   # the rescaled combined model output
             if plan.win is not None:
                 ent["win"] = plan.win   # the window plan and the static buffers of the gather and the merge
+            if blend:
+                # the fused blend-and-gather node reads row step_idx of the q-noise table the feed fills
+                ent["qnoise_all"] = torch.empty_like(ent["noise_all"])
+                plan.win.qnoise, plan.win.step_idx = ent["qnoise_all"], ent["step_idx"]
 
             def step(e=ent):
                 x_c = e["x_cur"]
@@ -214,8 +224,8 @@ class DDIMSampler(SamplerBase):
         # (ADVICE r3 + r4: opt-OUT, not opt-in — a silent interleaving gives a different noise stream with no diagnostic;
         # INTEGRATION.md §5; ALDM_NOISE_THREAD=0 forces the unthreaded feed for every run).
         cb_rng = any(getattr(f, "uses_rng", True) for f in (callback, img_callback) if f is not None)
-        feed = _NoiseFeed(plan.draw, total_steps, shape, mask is not None, temperature, dev, noise_buf=ent["noise_all"],
-                          **({"threaded": False, "chunk": 1} if cb_rng else {}))
+        feed = _NoiseFeed(plan.draw, total_steps, shape, mask is not None or blend, temperature, dev, noise_buf=ent["noise_all"],
+                          qnoise_buf=ent.get("qnoise_all"), **({"threaded": False, "chunk": 1} if cb_rng else {}))
         feed.produce_next()
         qn = feed.qnoise
         run_step = ent["run_step"]

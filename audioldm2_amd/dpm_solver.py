@@ -137,6 +137,13 @@ class DPMSolverSampler(SamplerBase):
         t_cur = t_tab[0].clone()
         eps_g = torch.empty_like(img) if rescale else None   # the rescaled combined model output
 
+        qbuf = None
+        if plan.win is not None and plan.win.blend:
+            # a plan with a source: the step's q-noise draw is staged into this one-row static buffer before the launch; the
+            # fused blend-and-gather node reads it (q_rows = 1) and row step_idx of blend_coef
+            qbuf = torch.empty_like(img)
+            plan.win.qnoise, plan.win.step_idx = qbuf, step_idx
+
         def step():
             eps = self.model_output(x_cur, t_cur, b, cond, unconditional_conditioning, use_cfg, prepared, win=plan.win)
             if rescale:
@@ -148,6 +155,8 @@ class DPMSolverSampler(SamplerBase):
             if mask is not None:
                 # img = q_sample(x0, ts)*mask + (1-mask)*img, between the replays; its draw comes first
                 ops.inpaint_blend(x_cur, plan.x0_d, draw().to(dev), plan.mask_d, plan.blend_coef[i])
+            if qbuf is not None:
+                qbuf.copy_(draw())   # the same draw; the blend itself is a node of the step
             run_step()
             log_step(i, total_steps, log_every_t, x_cur, pred_x0, intermediates, callback, img_callback)
         out = x_cur.clone()

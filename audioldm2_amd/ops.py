@@ -1643,6 +1643,49 @@ def window_gather(x: torch.Tensor, plan, out: Optional[torch.Tensor] = None) -> 
     return out
 
 
+def window_blend_gather(x: torch.Tensor, x0: torch.Tensor, qnoise: torch.Tensor, mask: torch.Tensor, blend_coef: torch.Tensor, plan,
+                        step_idx: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The inpainting blend on a long latent and its window gather in one launch (aldm_window_blend_gather): in place
+    x = (sa*x0 + so*qn)*mask + (1 - mask)*x, then the windows of the blended x -> [W*B, C, Tw, F] — bitwise inpaint_blend followed by
+    window_gather.  x, x0, mask [B, C, T, F]; qnoise [q_rows, B, C, T, F], or [B, C, T, F] for one row; blend_coef [coef_rows, 2] =
+    {sa, so}, or [2] for one row; step_idx (int32 [1] on the device, None: 0) selects row min(step_idx, rows - 1) of each table on
+    the device.  `out`: write the windows into this.  out may overlap no operand, x none of x0, qnoise, mask."""
+    for t, n in ((x, "x"), (x0, "x0"), (qnoise, "qnoise"), (mask, "mask"), (blend_coef, "blend_coef")):
+        _chk(t, "window_blend_gather." + n)
+    if x.dim() != 4 or x.shape[2] != plan.T or x.numel() == 0:
+        raise RuntimeError(f"window_blend_gather: x must be [B, C, T={plan.T}, F], got {tuple(x.shape)}")
+    B, C, T, F = x.shape
+    for t, n in ((x0, "x0"), (mask, "mask")):
+        if tuple(t.shape) != tuple(x.shape):
+            raise RuntimeError(f"window_blend_gather.{n}: expected {tuple(x.shape)}, got {tuple(t.shape)}")
+    if tuple(qnoise.shape) == tuple(x.shape):
+        q_rows = 1
+    elif qnoise.dim() == 5 and tuple(qnoise.shape[1:]) == tuple(x.shape) and qnoise.shape[0] >= 1:
+        q_rows = qnoise.shape[0]
+    else:
+        raise RuntimeError(f"window_blend_gather.qnoise: expected [q_rows, {B}, {C}, {T}, {F}] or one row of it, got "
+                           f"{tuple(qnoise.shape)}")
+    if blend_coef.numel() < 2 or blend_coef.shape[-1] != 2 or blend_coef.dim() > 2:
+        raise RuntimeError(f"window_blend_gather.blend_coef: expected [coef_rows, 2], got {tuple(blend_coef.shape)}")
+    coef_rows = blend_coef.numel() // 2
+    if step_idx is not None and (step_idx.dtype != torch.int32 or not step_idx.is_cuda or step_idx.numel() != 1):
+        raise RuntimeError("window_blend_gather.step_idx: expected one int32 on the device")
+    shape = (plan.W * B, C, plan.Tw, F)
+    if out is None:
+        out = torch.empty(shape, device=x.device, dtype=torch.float32)
+    _chk(out, "window_blend_gather.out")
+    if tuple(out.shape) != shape:
+        raise RuntimeError(f"window_blend_gather.out: expected {shape}, got {tuple(out.shape)}")
+    others = [(x0, "x0"), (qnoise, "qnoise"), (mask, "mask")]
+    _no_overlap(out, "window_blend_gather.out", [(x, "x")] + others + [(blend_coef, "blend_coef")])
+    _no_overlap(x, "window_blend_gather.x", others + [(blend_coef, "blend_coef")])
+    _l.check(_l.load().aldm_window_blend_gather(x.data_ptr(), x0.data_ptr(), qnoise.data_ptr(), mask.data_ptr(),
+                                                blend_coef.data_ptr(), _p(step_idx), q_rows, coef_rows, out.data_ptr(),
+                                                _window_starts(plan), B, plan.W, C, T, plan.Tw, F, _stream()),
+             "window_blend_gather")
+    return out
+
+
 def window_merge(win: torch.Tensor, plan, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The tapered, normalised overlap-add of window-wise tensors (aldm_window_merge): win [W*B, C, Tw, F] -> [B, C, T, F], or
     win [2, W*B, C, Tw, F] (the [uncond ; cond] pair of a guided UNet pass) -> [2, B, C, T, F]; rows window-major as

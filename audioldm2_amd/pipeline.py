@@ -1066,7 +1066,11 @@ class LatentDiffusion(nn.Module):
                                      unconditional_guidance_scale=unconditional_guidance_scale,
                                      unconditional_conditioning=unconditional_conditioning, use_plms=use_plms, windows=plan,
                                      **_sample_log_keywords(sampler, guidance_rescale))
-        # the tail: the VAE at its trained shape on the W*B0 windows of the final latent, the mels cross-faded on the scaled plan
+        return self._long_tail(samples, plan, mel_plan, batch)
+
+    def _long_tail(self, samples, plan, mel_plan, batch):
+        """The tail of a long-form job: the VAE at its trained shape on the W*B0 windows of the final latent, the mels cross-faded
+        on the scaled plan, one vocoder pass, the cut."""
         mel_w = self.decode_first_stage_cl(ops.window_gather(samples, plan))   # [W*B0, Tw*f, F_mel, 1] channels-last
         mel = ops.window_merge(mel_w.view(mel_w.shape[0], 1, mel_w.shape[1], mel_w.shape[2]), mel_plan)   # [B0, 1, T*f, F_mel]
         self.last_long_latent, self.last_long_mel = samples, mel
@@ -1074,6 +1078,86 @@ class LatentDiffusion(nn.Module):
         # a long clip has exactly one vocoder hop per mel frame: the few samples the vocoder's first transposed convolution
         # appends (kernel 16 at stride 5: 32 of them at 16 kHz) are cut
         return waveform[..., :mel.shape[-2] * int(np.prod(self.first_stage_model.vocoder.h.upsample_rates))]
+
+    @torch.no_grad()
+    def encode_long(self, mel, plan, mel_plan, n_post):
+        """The scaled posterior sample of a mel longer than the VAE's trained shape: mel [B0, 1, T*f, F_mel] (device) -> z
+        [B0, C, T, F] = scale_factor * (mean + std * n_post), n_post [B0, C, T, F] (device).  The encoder only ever sees its
+        trained shape: the mel's windows are gathered on the mel plan (ops.window_gather), `encode_moments_cl` runs on the W*B0
+        windows, and the window-wise channels-last moments [W*B0, Tw, w, 2C] — viewed as [W*B0, 1, Tw, w*2C] on the latent plan —
+        are fused into long moments by ops.window_merge: mean and logvar each become the plan's convex combination of the windows'
+        values, and where one window covers a frame they are that window's own, bit for bit.  ops.posterior_qsample then samples
+        the long moments.  Its forward-diffusion output is not needed here; it is called with n_enc = n_post and the coefficients
+        {scale, 1, 0}, which make that output a second copy of z (one extra latent write per job) — no z-only kernel form."""
+        B0, C, T, F = n_post.shape
+        if mel.dim() != 4 or mel.shape[0] != B0 or mel.shape[2] != mel_plan.T or plan.T != T or mel_plan.T != plan.T * mel_plan.scale:
+            raise ValueError(f"encode_long: mel {tuple(mel.shape)} / n_post {tuple(n_post.shape)} do not fit the plans "
+                             f"(T={plan.T}, mel T={mel_plan.T})")
+        mom_w = self.first_stage_model.encode_moments_cl(ops.window_gather(mel.float().contiguous(), mel_plan))
+        if tuple(mom_w.shape[1:]) != (plan.Tw, F, 2 * C):
+            raise ValueError(f"encode_long: the encoder's moments are {tuple(mom_w.shape)}, expected [W*B0, {plan.Tw}, {F}, {2 * C}]")
+        moments = ops.window_merge(mom_w.contiguous().view(mom_w.shape[0], 1, plan.Tw, F * 2 * C), plan).view(B0, T, F, 2 * C)
+        self.last_long_moments = moments
+        coef = torch.tensor([1.0 if torch.is_tensor(self.scale_factor) else float(self.scale_factor), 1.0, 0.0],
+                            dtype=torch.float32).to(self.device)
+        if torch.is_tensor(self.scale_factor):
+            coef[0:1].copy_(self.scale_factor.detach().reshape(1))
+        n_post = n_post.float().contiguous()
+        z, _ = ops.posterior_qsample(moments, n_post, n_post, coef)
+        return z
+
+    @torch.no_grad()
+    def generate_batch_long_from_audio(self, batch, latent_t_size, keep, hop=None, ddim_steps=200, ddim_eta=1.0,
+                                       unconditional_guidance_scale=1.0, use_plms=False, sampler=None, negative_prompt=None,
+                                       guidance_rescale=0.0, n_gen=1, shard=None):
+        """Continuation and inpainting of long clips: generate_batch_long around a source.  `batch["log_mel_spec"]`
+        is the long mel [B0, latent_t_size*f, F_mel] of the source; `keep` lists the half-open latent-frame intervals [a, b) to
+        keep (windows.keep_mask); everything else is generated under the prompt.  The source is encoded window by window
+        (encode_long) and rides on the window plan (windows.with_source): at every step the known region of the LONG latent is
+        replaced by q_sample(z, t) inside the replayed step, fused with the window gather (ops.window_blend_gather).  The tail is
+        generate_batch_long's: window-wise decode, mel cross-fade, one vocoder pass, the same cut.
+
+        As in the reference's inpainting (ddim.py:226-231) the final latent is NOT pasted over with the source: the kept region
+        is what the last blend (at the lowest noise level) and the last step leave — close to the source, not bitwise it.
+
+        Refused before any draw or GPU work: ddim_steps=None, n_gen != 1, shard=, bad lengths or hops (long_form_plans), a bad
+        `keep`, a mel whose length is not latent_t_size*f.
+
+        Host-generator order (RNG contract R): (R1) randn(B0, C, latent_t_size, F) at the LONG shape, the
+        posterior noise, really used; (R1b) the rand(1) of _cfg_dropout_draw on every call but an object's first; the
+        conditioners' draws (twice with a negative prompt); randn(B0, C, latent_t_size, F), the long x_T; per step at the long
+        shape: DDIM the q-noise then the step noise, PLMS the q-noise then its own draws, DPM-Solver++ the q-noise only."""
+        from .windows import keep_mask, with_source
+        if shard is not None:
+            raise ValueError("generate_batch_long_from_audio: shard= is not supported on this path")
+        if ddim_steps is None:
+            raise ValueError("generate_batch_long_from_audio needs ddim_steps: the ancestral sampler has no windowed form")
+        if n_gen != 1:
+            raise ValueError(f"generate_batch_long_from_audio: n_gen must be 1, got {n_gen}: the CLAP re-ranker scores clips of the "
+                             "trained length, candidate re-ranking of long clips is not supported")
+        sampler = resolve_sampler(sampler, use_plms)
+        kw = {} if negative_prompt is None else {"negative_prompt": negative_prompt}
+        neg_batch, guidance_rescale = _guidance_kwargs(dict(kw, guidance_rescale=guidance_rescale), unconditional_guidance_scale,
+                                                       batch, ddim_steps)
+        plan, mel_plan = self.long_form_plans(latent_t_size, hop)
+        mask_t = keep_mask(plan.T, keep)
+        fb = batch["log_mel_spec"] if self.first_stage_key == "fbank" else batch[self.first_stage_key]
+        f = 2 ** (self.first_stage_model.encoder.num_resolutions - 1)
+        if fb.dim() != 3 or fb.shape[-2] != plan.T * f or fb.shape[-1] % f != 0:
+            raise ValueError(f"generate_batch_long_from_audio: the mel must be [B0, latent_t_size*{f} = {plan.T * f}, F_mel], got "
+                             f"{tuple(fb.shape)}")
+        B0 = fb.shape[0]
+        n_post = torch.randn((B0, self.first_stage_model.embed_dim, plan.T, fb.shape[-1] // f))   # (R1) the posterior draw, long
+        self._cfg_dropout_draw()                                                                    # (R1b) every call but the first
+        c = self.get_learned_conditioning_dict(batch)
+        unconditional_conditioning = _unconditional_half(self, neg_batch, 1, B0, unconditional_guidance_scale)
+        z = self.encode_long(fb.unsqueeze(1).float().contiguous().to(self.device), plan, mel_plan, n_post.to(self.device))
+        self.last_long_source = z
+        samples, _ = self.sample_log(cond=c, batch_size=B0, x_T=None, ddim=True, ddim_steps=ddim_steps, eta=ddim_eta,
+                                     unconditional_guidance_scale=unconditional_guidance_scale,
+                                     unconditional_conditioning=unconditional_conditioning, use_plms=use_plms,
+                                     windows=with_source(plan, z, mask_t), **_sample_log_keywords(sampler, guidance_rescale))
+        return self._long_tail(samples, plan, mel_plan, batch)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1345,6 +1429,76 @@ def text_to_audio_long(latent_diffusion, text, duration, overlap=2.5, transcript
     with torch.no_grad():
         return latent_diffusion.generate_batch_long(batch, latent_t, hop=hop, unconditional_guidance_scale=guidance_scale,
                                                     ddim_steps=ddim_steps, **sampler_kw)
+
+
+def _source_seconds(source):
+    """The length of an audio source in seconds, host only: a path to a .wav (its own rate), or a 1-D array at 16 kHz."""
+    if isinstance(source, (str, os.PathLike)):
+        from scipy.io import wavfile
+        sr, data = wavfile.read(source)
+        return data.shape[0] / float(sr)
+    return np.asarray(source).reshape(-1).shape[0] / 16000.0
+
+
+def keep_frames(keep, per_second, latent_t):
+    """Pure host: `keep` intervals (start_s, end_s) in seconds -> half-open latent-frame intervals [ceil(start*fps),
+    floor(end*fps)), the frames that lie wholly inside the interval, the end clipped to `latent_t`.  ValueError for an interval
+    that is not a pair of finite numbers; windows.keep_mask refuses what is empty, unordered, overlapping or out of range."""
+    out = []
+    for iv in keep:
+        try:
+            a, b = (float(v) for v in iv)
+        except (TypeError, ValueError):
+            raise ValueError(f"keep: an interval must be a pair (start_s, end_s) of seconds, got {iv!r}")
+        if not (np.isfinite(a) and np.isfinite(b)):
+            raise ValueError(f"keep: interval bounds must be finite, got {iv!r}")
+        # 1e-9 of a frame: a bound that is a whole frame in exact arithmetic (5 s at 25.6 frames per second) stays that frame
+        out.append((int(math.ceil(a * per_second - 1e-9)), min(int(math.floor(b * per_second + 1e-9)), int(latent_t))))
+    return out
+
+
+def extend_audio(latent_diffusion, text, original_audio_file_path, duration, keep=None, overlap=2.5, transcription="", seed=42,
+                 ddim_steps=200, guidance_scale=3.5, sampler=None, negative_prompt=None, guidance_rescale=0.0):
+    """Continue or inpaint a long clip: a clip of `duration` seconds — longer than the model's trained length — that keeps parts
+    of the recording `original_audio_file_path` (a path, or a 1-D float waveform at 16 kHz; zero-padded or cut to `duration`) and
+    generates the rest under the prompt `text` by windowed diffusion (LatentDiffusion.generate_batch_long_from_audio).  `keep`
+    lists the intervals (start_s, end_s), in seconds, to keep; they become the latent frames [ceil(start*fps), floor(end*fps)),
+    fps = latent_t_per_second.  The default is the whole source, from 0 to its own length before padding: a continuation ("here
+    are my 8 seconds, carry them on to 30").  Intervals inside a long source give long inpainting ("keep this recording, but
+    regenerate seconds 12 to 19": keep=[(0, 12), (19, 40)]).  `duration`, `overlap`, `sampler`, `negative_prompt` and
+    `guidance_rescale` as in text_to_audio_long; the front end is audio_to_audio's (wav_to_fbank, the 16 kHz TacotronSTFT): a
+    model whose first stage is not 16 kHz / 64 mel bins is refused.  Everything is refused before any draw or GPU work.  The kept
+    region is not pasted back at the end (see generate_batch_long_from_audio).  The model's own latent_t_size is not changed.
+    Returns np.float32 [1, 1, samples]."""
+    from .stft import TacotronSTFT
+    from .windows import keep_mask
+    sampler_kw = _sampler_kwargs(sampler, negative_prompt, guidance_rescale)
+    if ddim_steps is None:
+        raise ValueError("extend_audio needs ddim_steps: the ancestral sampler has no windowed form")
+    from .sampling import check_guidance_rescale
+    check_guidance_rescale(guidance_rescale)
+    per_second = float(latent_diffusion.latent_t_per_second)
+    latent_t = int(duration * per_second)
+    hop = latent_diffusion.latent_t_size - int(round(overlap * per_second))
+    latent_diffusion.long_form_plans(latent_t, hop)   # refuse before any GPU work
+    f = 2 ** (latent_diffusion.first_stage_model.encoder.num_resolutions - 1)
+    mel_bins = int(latent_diffusion.latent_f_size) * f
+    if int(latent_diffusion.sampling_rate) != 16000 or mel_bins != 64:
+        raise ValueError("extend_audio: the mel front end is the 16 kHz / 64-bin one; this model's first stage takes "
+                         f"{latent_diffusion.sampling_rate} Hz / {mel_bins} bins")
+    if keep is None:
+        keep = [(0.0, min(_source_seconds(original_audio_file_path), float(duration)))]
+    frames = keep_frames(keep, per_second, latent_t)
+    keep_mask(latent_t, frames)   # refuse a bad keep before any draw
+    seed_everything(int(seed))
+    fn_STFT = TacotronSTFT(1024, 160, 1024, 64, 16000, 0, 8000)  # utils.py:262-270 "preprocessing"
+    mel, _, _ = wav_to_fbank(original_audio_file_path, target_length=latent_t * f, fn_STFT=fn_STFT)
+    batch = make_batch_for_text_to_audio(text, transcription=transcription, batchsize=1)
+    batch["log_mel_spec"] = batch["fbank"] = mel[None, ...].float().cpu()
+    with torch.no_grad():
+        return latent_diffusion.generate_batch_long_from_audio(batch, latent_t, frames, hop=hop,
+                                                               unconditional_guidance_scale=guidance_scale,
+                                                               ddim_steps=ddim_steps, **sampler_kw)
 
 
 def audio_to_audio(latent_diffusion, text, original_audio_file_path, strength=0.5, transcription="", seed=42,

@@ -110,12 +110,19 @@ class PLMSSampler(SamplerBase):
         t_cur = t_tab[0].clone()
         eps_g = torch.empty_like(img) if rescale else None   # the rescaled combined model output of the replayed step
 
-        def guided_eps(x, t_row, out=None, idx=None):
+        qbuf = None
+        if win is not None and win.blend:
+            # a plan with a source: the step's q-noise draw is staged into this one-row static buffer before the launch; the
+            # fused blend-and-gather of the step's first pass reads it (q_rows = 1) and row step_idx of blend_coef
+            qbuf = torch.empty_like(img)
+            win.qnoise, win.step_idx = qbuf, step_idx
+
+        def guided_eps(x, t_row, out=None, idx=None, first_pass=True):
             """eps [2, b, ...] for the step kernel to combine, or with rescale the combined and rescaled [b, ...] (row: the
             counter's, or row 0 — the step's row in the eager calls of step 0).  The eager calls (idx is None) keep their
             results side by side: a windowed run merges them into fresh tensors, not the step graph's static one"""
             eps = self.model_output(x, t_row, b, cond, unconditional_conditioning, use_cfg, prepared, win=win,
-                                    static=idx is not None)
+                                    static=idx is not None, first_pass=first_pass)
             if not rescale:
                 return eps
             return ops.cfg_rescale_indexed(eps, torch.empty_like(img) if out is None else out, coef, idx)
@@ -129,13 +136,15 @@ class PLMSSampler(SamplerBase):
             if mask is not None:
                 # img = q_sample(x0, ts)*mask + (1-mask)*img   (plms.py:222-227, ddpm.py:430-436); its draw comes first
                 ops.inpaint_blend(x_cur, plan.x0_d, draw().to(dev), plan.mask_d, plan.blend_coef[i])
+            if qbuf is not None:
+                qbuf.copy_(draw())   # the same draw, first in the step; the blend itself runs inside the step's first pass
             if i == 0:
                 # pseudo improved Euler (plms.py:341-345): provisional x_prev from e_t, a second pass at (x_prev, t_next)
                 e_t = guided_eps(x_cur, t_cur)
                 x_tmp, _ = ops.plms_first_step(x_cur, e_t, None, coef[0])
                 draw()                                                   # the noise_like of the provisional update
                 t_next = t_tab[min(1, total_steps - 1)]
-                e_next = guided_eps(x_tmp, t_next)
+                e_next = guided_eps(x_tmp, t_next, first_pass=False)   # on the provisional x_prev: a plain gather, no blend
                 ops.plms_first_step(x_cur, e_t, e_next, coef[0], x_out=x_cur, pred_x0=pred_x0, hist=hist)
                 ops.step_advance(step_idx, t_tab, t_cur)
                 del e_t, e_next, x_tmp

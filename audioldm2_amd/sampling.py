@@ -379,7 +379,7 @@ class SamplerBase(object):
         if quantize_denoised or score_corrector is not None or noise_dropout != 0.0:
             raise NotImplementedError(f"{name}(HIP): option not used by the AudioLDM2 pipeline")
 
-    def model_output(self, x, t_row, b, cond, uncond, use_cfg, prepared, win=None, static=True):
+    def model_output(self, x, t_row, b, cond, uncond, use_cfg, prepared, win=None, static=True, first_pass=True):
         """The UNet pass of one step: eps [2, b, ...] = [uncond ; cond] under guidance (combined inside the step kernel, or by
         ops.cfg_rescale_indexed), else eps [b, ...].  t_row: the step's timestep as floats, one entry per UNet row.  Guidance is ONE
         pass over 2b samples when the model has `apply_model_cfg` — asked at every call: it may be set on an instance — where the
@@ -388,9 +388,20 @@ class SamplerBase(object):
         `win` (plan_run's `p.win`, a windowed run): x is the long latent; its windows are gathered (ops.window_gather), the pass
         above runs on the W*b window rows — cond, uncond, prepared and t_row are the W-fold tiled ones — and the window outputs
         are merged back to the long shape (ops.window_merge): two launches around an unchanged pass.  `static`: gather and merge
-        into win's buffers (a step graph's static tensors); False: into fresh ones (eager calls whose results must coexist)."""
+        into win's buffers (a step graph's static tensors); False: into fresh ones (eager calls whose results must coexist).
+
+        A plan with a source (`win.blend`, windows.with_source): at a step's first UNet pass (`first_pass`) the fused
+        ops.window_blend_gather takes the gather's place — it blends q_sample(x0, t) into x IN PLACE where the mask is 1, with the
+        q-noise row and the coefficient row the device-side `win.step_idx` selects from `win.qnoise` and `win.blend_coef`, and
+        writes the windows of the blended latent.  Any further pass of the same step (PLMS's second one in its eager step 0, on the
+        provisional x_prev) gathers plainly.  The sampler sets win.qnoise and win.step_idx before its first step."""
         if win is not None:
-            xw = ops.window_gather(x, win.plan, out=win.xw if static else None)
+            if win.blend and first_pass:
+                # a plan with a source: the blend of the known region on the long latent, in place, and the gather are one launch
+                xw = ops.window_blend_gather(x, win.x0, win.qnoise, win.mask, win.blend_coef, win.plan, step_idx=win.step_idx,
+                                             out=win.xw if static else None)
+            else:
+                xw = ops.window_gather(x, win.plan, out=win.xw if static else None)
             eps_w = self.model_output(xw, t_row, win.plan.W * b, cond, uncond, use_cfg, prepared)
             return ops.window_merge(eps_w.contiguous(), win.plan, out=win.merged if static else None)
         if not use_cfg:
@@ -409,7 +420,9 @@ class SamplerBase(object):
         the per-step noise keep the long shape; `p.cond` / `p.uncond` are the conditionings tiled W times (window-major), t_tab
         has W times the columns, prepare_cfg sees the tiled pair, and `p.win` holds the plan and the two static window buffers
         of model_output (xw [W*b, C, Tw, F], merged [2, b, ...] or [b, ...]).  Without a plan p.cond / p.uncond are the arguments
-        and p.win is None.  Not together with mask / x0.
+        and p.win is None.  Not together with mask / x0: a source to keep rides on the plan (windows.with_source) and fills
+        p.mask_d / p.x0_d / p.blend_coef as a mask does, with p.win.blend set — the blend then runs inside the step, fused with
+        the gather (model_output), not between the steps.
 
         The cut of the schedule: `t_start=k` keeps exactly its first k entries, as `decode` cuts it (ddim.py:466-467; see
         check_t_start); `timesteps` keeps its first int(min(timesteps / S, 1) * S) - 1 entries (ddim.py:198-206).  `total_steps`
@@ -421,13 +434,18 @@ class SamplerBase(object):
         in this order: img, coef, t_tab, mask_d, x0_d, blend_coef, then the model's prepare_cfg."""
         dev = torch.device("cuda")
         shape = tuple(shape)
-        W = 1
+        W, source = 1, None
         if windows is not None:
             if mask is not None or x0 is not None:
                 raise ValueError("windows= together with mask / x0: inpainting over windows is not supported")
             if len(shape) != 4 or shape[2] != windows.T:
                 raise ValueError(f"windows= is a plan over T={windows.T} frames, the latent shape is {shape}")
             W = windows.W
+            if getattr(windows, "x0", None) is not None:
+                # a source rides on the plan (windows.with_source): inpainting / continuation over windows
+                if tuple(windows.x0.shape) != shape:
+                    raise ValueError(f"windows=: the plan's source x0 is {tuple(windows.x0.shape)}, the latent shape is {shape}")
+                source = (windows.mask, windows.x0)
         ts = self.ddim_timesteps
         t_start = check_t_start(t_start, timesteps, ts.shape[0])
         if t_start is not None:
@@ -449,6 +467,8 @@ class SamplerBase(object):
         p.coef = table(total_steps, use_cfg).to(dev)
         tr = torch.from_numpy(p.time_range)
         p.t_tab = tr.float()[:, None].repeat(1, (2 if use_cfg else 1) * W * shape[0]).to(dev).contiguous()
+        if source is not None:
+            mask, x0 = source
         if mask is not None:
             assert x0 is not None
             p.mask_d = mask.float().to(dev).expand(shape).contiguous()
@@ -459,8 +479,12 @@ class SamplerBase(object):
             from .windows import tile_cond
             p.cond, p.uncond = tile_cond(cond, W), tile_cond(unconditional_conditioning, W)
             b, C, _, F = shape
+            # blend: the plan carries a source; the fused blend-and-gather node reads x0 / mask / blend_coef from here and the
+            # q-noise table and the step counter the sampler puts next to them (model_output)
             p.win = SimpleNamespace(plan=windows, xw=torch.empty((W * b, C, windows.Tw, F), device=dev, dtype=torch.float32),
-                                    merged=torch.empty(((2,) if use_cfg else ()) + shape, device=dev, dtype=torch.float32))
+                                    merged=torch.empty(((2,) if use_cfg else ()) + shape, device=dev, dtype=torch.float32),
+                                    blend=source is not None, x0=p.x0_d, mask=p.mask_d, blend_coef=p.blend_coef, qnoise=None,
+                                    step_idx=None)
         if use_cfg and hasattr(self.model, "apply_model_cfg") and hasattr(self.model, "prepare_cfg"):
             p.prepared = self.model.prepare_cfg(p.cond, p.uncond)
         return p

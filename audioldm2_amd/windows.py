@@ -4,6 +4,9 @@ A long latent [b, C, T, F] is denoised through W overlapping windows of the UNet
 step the windows are gathered (ops.window_gather), the UNet runs on the W*b window rows, and the window-wise outputs are fused by a
 tapered, normalised overlap-add (ops.window_merge) before the sampler's update of the long latent.  The plan is everything the two
 kernels need: the window starts and the normalised weights.
+
+A plan may carry a source to keep (`with_source`, `keep_mask`): continuation and inpainting of long clips.  The
+samplers then blend q_sample(source, t) into the long latent in front of every step's gather (ops.window_blend_gather).
 """
 from __future__ import annotations
 
@@ -75,6 +78,58 @@ def window_plan(T, Tw, hop, scale=1):
 def plan_key(plan):
     """What identifies a plan's launch sequence (the starts are kernel arguments captured with a step graph)."""
     return (plan.T, plan.Tw, tuple(plan.starts))
+
+
+def keep_mask(T, intervals):
+    """The [T] fp32 0/1 vector of a source's kept frames: 1 inside the half-open latent-frame intervals [a, b) of `intervals`, 0
+    elsewhere (1 = keep the source, 0 = generate).  The intervals must be integer pairs with 0 <= a < b <= T, in ascending order,
+    and may touch but not overlap.  ValueError otherwise."""
+    T = _check_int(T, "T")
+    m = torch.zeros(T, dtype=torch.float32)
+    end = 0
+    for iv in intervals:
+        try:
+            a, b = iv
+        except (TypeError, ValueError):
+            raise ValueError(f"keep_mask: an interval must be a pair (start, end) of latent frames, got {iv!r}")
+        for v in (a, b):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"keep_mask: interval bounds must be integers (latent frames), got {iv!r}")
+        a, b = int(a), int(b)
+        if a >= b:
+            raise ValueError(f"keep_mask: the interval [{a}, {b}) is empty")
+        if a < 0 or b > T:
+            raise ValueError(f"keep_mask: the interval [{a}, {b}) leaves [0, {T})")
+        if a < end:
+            raise ValueError(f"keep_mask: the interval [{a}, {b}) starts before the previous one ends ({end}): intervals must be "
+                             "ordered and may not overlap")
+        m[a:b] = 1.0
+        end = b
+    return m
+
+
+def with_source(plan, x0, mask):
+    """`plan` with a source to keep (continuation and inpainting of long clips): a plan object with the same T, Tw,
+    starts and wn — and so the same plan_key — that additionally carries `x0` [b, C, T, F] (the source's scaled latent) and `mask`
+    (broadcastable to x0's shape; 1 = keep the source, 0 = generate; a [T] vector, as keep_mask returns it, is taken along the time
+    axis).  A sampler given such a plan as `windows=` blends q_sample(x0, t) into the long latent in front of every step's gather
+    (ops.window_blend_gather).  ValueError for shapes that do not fit plan.T."""
+    if not torch.is_tensor(x0) or x0.dim() != 4 or x0.shape[2] != plan.T:
+        raise ValueError(f"with_source: x0 must be a tensor [b, C, T={plan.T}, F], got "
+                         f"{tuple(x0.shape) if torch.is_tensor(x0) else type(x0).__name__}")
+    if not torch.is_tensor(mask):
+        raise ValueError(f"with_source: mask must be a tensor, got {type(mask).__name__}")
+    if mask.dim() == 1:
+        if mask.shape[0] != plan.T:
+            raise ValueError(f"with_source: a 1-D mask is one entry per latent frame, T={plan.T}, got {tuple(mask.shape)}")
+        mask = mask.view(1, 1, plan.T, 1)
+    try:
+        ok = tuple(torch.broadcast_shapes(tuple(mask.shape), tuple(x0.shape))) == tuple(x0.shape)
+    except RuntimeError:
+        ok = False
+    if not ok:
+        raise ValueError(f"with_source: mask {tuple(mask.shape)} does not broadcast to x0 {tuple(x0.shape)}")
+    return SimpleNamespace(**dict(plan.__dict__, x0=x0, mask=mask))
 
 
 def device_weights(plan, device):

@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 /* ---- library / error ------------------------------------------------------------------ */
-int aldm_version(void);              /* ABI version (18), bumped on any struct / entry change */
+int aldm_version(void);              /* ABI version (19), bumped on any struct / entry change */
 const char* aldm_last_error(void);   /* message of the last failing call on this thread     */
 
 /* ---- activations usable as prologue (applied to the gathered input) or epilogue -------- */
@@ -577,6 +577,17 @@ int aldm_window_gather(const float* x, float* win, aldm_window_starts starts, in
  * decodes in the mel domain (C = 1, F = mel bins, the plan scaled by the VAE's time factor).                                    */
 int aldm_window_merge(const float* win, const float* wn, float* out, aldm_window_starts starts, int H, int B, int W, int C, int T,
                       int Tw, int F, void* stream);
+/* The inpainting blend on the long latent fused with the window gather (ABI v19): one launch per step of a windowed
+ * run that keeps a source.  s = step_idx ? *step_idx : 0; the q-noise row is qnoise[min(s, q_rows-1)] of [q_rows, B, C, T, F], the
+ * coefficients blend_coef[min(s, coef_rows-1)] of [coef_rows, 2] = {sa = sqrt(abar_t), so = sqrt(1 - abar_t)} (q_rows == 1: one
+ * staged draw per step).  In place on x, then every window copy of the blended value:
+ *   x[b,c,t,f] = (sa*x0 + so*qn)*m + (1 - m)*x;   win[(j*B + b), c, t - s_j, f] = x[b,c,t,f] for every j with 0 <= t - s_j < Tw
+ * mask, x0 [B, C, T, F].  Scatter form: one thread owns a long-latent element, every window element has one writer and all are
+ * written; no atomics.  The expression and its order are aldm_inpaint_blend's: the launch is bitwise aldm_inpaint_blend followed by
+ * aldm_window_gather.  win may overlap none of x, x0, qnoise, mask; x none of x0, qnoise, mask; checked before the launch.        */
+int aldm_window_blend_gather(float* x, const float* x0, const float* qnoise, const float* mask, const float* blend_coef,
+                             const int* step_idx, int q_rows, int coef_rows, float* win, aldm_window_starts starts, int B, int W,
+                             int C, int T, int Tw, int F, void* stream);
 /* generic y = alpha*a + beta*b (b may be NULL) */
 int aldm_axpby(const float* a, const float* b, float* y, float alpha, float beta, int64_t n,
                void* stream);
