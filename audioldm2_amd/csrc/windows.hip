@@ -1,6 +1,6 @@
 // windows.hip — the per-step launches of windowed (long-form) diffusion: the window gather in front of the UNet pass and the
 // tapered, normalised overlap-add behind it, and the gather fused with the inpainting blend of a kept source on
-// the long latent (§9f).  All are HBM-bound copies with at most `cover` multiply-adds (the blend: five operations) per
+// the long latent (§9f), and the wrap-around forms of the three for ring plans (§9g).  All are HBM-bound copies with at most `cover` multiply-adds (the blend: five operations) per
 // element: 16-byte accesses along the contiguous F axis where F % 4 == 0 and the pointers are aligned, a scalar path otherwise,
 // grid-stride, 64-bit indexing, fp32.  The window starts travel as a kernel argument (aldm_window_starts, by value): a captured
 // step graph carries them, there is no device table and no copy inside a capture; every index into them is wave-uniform.
@@ -114,6 +114,125 @@ __global__ void window_blend_gather_kernel(float* __restrict__ x, const float* _
     }
 }
 
+// ---- ring plans (seamless loops): the T frames are a circle, window j covers the frames (s_j + p) mod T ------------
+// Siblings of the three kernels above rather than a template flag on them: the linear kernels stay, instruction for instruction,
+// what they were.  The wrap is along T, so a 16-byte access along F never straddles it; it is a compare and a subtract (add), never
+// an integer modulo: 0 <= s_j < T and 0 <= p < Tw <= T bound s_j + p below 2T, and t - s_j above -T.
+
+// win[(j*B + b), c, p, f] = x[b, c, (s_j + p) mod T, f].  A window's Tw*F floats per (b, c) come from at most two contiguous spans
+// of x: frames [s_j, min(s_j + Tw, T)) and [0, s_j + Tw - T).  len1 = the first span in units; the span is picked by comparing the
+// in-row offset with it (wave-uniform but for the one wave that holds the junction): no division beyond the linear kernel's.
+template <int V>
+__global__ void window_gather_ring_kernel(const float* __restrict__ x, float* __restrict__ win, aldm_window_starts st, int T, int Tw,
+                                          int F, int64_t per_row, int64_t total) {
+    typedef typename vec_of<V>::type vec;
+    const int j = blockIdx.y;
+    const int s = st.s[j];
+    const int64_t src0 = (int64_t)s * F;
+    const int64_t plane = (int64_t)T * F;
+    const int64_t len1 = (int64_t)(Tw < T - s ? Tw : T - s) * F / V;
+    float* dst = win + (int64_t)j * total * V;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t bc = i / per_row, off = i - bc * per_row;
+        const int64_t src = off < len1 ? src0 + off * V : (off - len1) * V;
+        *reinterpret_cast<vec*>(dst + i * V) = *reinterpret_cast<const vec*>(x + bc * plane + src);
+    }
+}
+
+// window_merge_kernel on a ring: the windows j in ascending order with p = t - s_j (+ T if negative) < Tw.  Tw <= T: a window
+// covers a frame at most once.
+template <int V>
+__global__ void window_merge_ring_kernel(const float* __restrict__ win, const float* __restrict__ wn, float* __restrict__ out,
+                                         aldm_window_starts st, int B, int W, int C, int T, int Tw, int F, int64_t total) {
+    typedef typename vec_of<V>::type vec;
+    const int FV = F / V;
+    const int64_t wplane = (int64_t)Tw * F;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        int64_t q = i / FV;
+        const int fv = (int)(i - q * FV);
+        const int t = (int)(q % T);
+        q /= T;
+        const int c = (int)(q % C);
+        q /= C;
+        const int b = (int)(q % B);
+        const int64_t h = q / B;
+        vec acc = vec(0.0f);
+        bool first = true;
+        for (int j = 0; j < W; ++j) {
+            int p = t - st.s[j];
+            if (p < 0) p += T;
+            if (p >= Tw) continue;
+            const float wv = wn[(int64_t)j * Tw + p];
+            const vec e = *reinterpret_cast<const vec*>(win + ((((h * W + j) * B + b) * C + c) * wplane + (int64_t)p * F + fv * V));
+            if (first) {
+                acc = wv * e;
+                first = false;
+            } else if constexpr (V == 4) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) acc[k] = __builtin_fmaf(wv, e[k], acc[k]);
+            } else {
+                acc = __builtin_fmaf(wv, e, acc);
+            }
+        }
+        *reinterpret_cast<vec*>(out + i * V) = acc;
+    }
+}
+
+// window_blend_gather_kernel on a ring: the same blend expression, operation order and row selection, then every window copy of
+// the owned element at its wrapped position.  A window position still maps to one frame, so every element of win has exactly one
+// writer, and the windows cover the circle, so every element is written.
+template <int V>
+__global__ void window_blend_gather_ring_kernel(float* __restrict__ x, const float* __restrict__ x0, const float* __restrict__ qnoise,
+                                                const float* __restrict__ mask, const float* __restrict__ blend_coef,
+                                                const int* __restrict__ step_idx, int q_rows, int coef_rows,
+                                                float* __restrict__ win, aldm_window_starts st, int B, int W, int C, int T, int Tw,
+                                                int F, int64_t total) {
+    typedef typename vec_of<V>::type vec;
+    int s = step_idx ? *step_idx : 0;
+    s = s < 0 ? 0 : s;
+    const int qr = s < q_rows ? s : q_rows - 1, cr = s < coef_rows ? s : coef_rows - 1;
+    const float sa = blend_coef[2 * cr], so = blend_coef[2 * cr + 1];
+    const float* qn = qnoise + (int64_t)qr * total * V;
+    const int FV = F / V;
+    const int64_t wplane = (int64_t)Tw * F;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        int64_t q = i / FV;
+        const int fv = (int)(i - q * FV);
+        const int t = (int)(q % T);
+        q /= T;
+        const int c = (int)(q % C);
+        const int64_t b = q / C;
+        const vec m = *reinterpret_cast<const vec*>(mask + i * V);
+        const vec orig = sa * *reinterpret_cast<const vec*>(x0 + i * V) + so * *reinterpret_cast<const vec*>(qn + i * V);
+        const vec v = orig * m + (1.0f - m) * *reinterpret_cast<const vec*>(x + i * V);
+        *reinterpret_cast<vec*>(x + i * V) = v;
+        for (int j = 0; j < W; ++j) {
+            int p = t - st.s[j];
+            if (p < 0) p += T;
+            if (p >= Tw) continue;
+            *reinterpret_cast<vec*>(win + (((int64_t)j * B + b) * C + c) * wplane + (int64_t)p * F + fv * V) = v;
+        }
+    }
+}
+
+// the host-side checks the ring entries share: the shape, and starts whose windows of Tw cover the circle of T frames
+static int window_ring_args_ok(const char* name, const aldm_window_starts& st, int B, int W, int C, int T, int Tw, int F) {
+    ALDM_CHECK(B > 0 && C > 0 && F > 0 && Tw > 0 && T >= Tw, "%s: bad shape (B=%d, C=%d, T=%d, Tw=%d, F=%d)", name, B, C, T, Tw, F);
+    ALDM_CHECK(W >= 2 && W <= ALDM_MAX_WINDOWS && st.n == W, "%s: W=%d windows with %d starts (2 <= W == n <= %d: a ring of one "
+               "window has no window across its junction)", name, W, st.n, ALDM_MAX_WINDOWS);
+    ALDM_CHECK(st.s[0] == 0, "%s: starts[0]=%d must be 0", name, st.s[0]);
+    for (int j = 1; j < W; ++j) {
+        ALDM_CHECK(st.s[j] > st.s[j - 1], "%s: starts must ascend (starts[%d]=%d after %d)", name, j, st.s[j], st.s[j - 1]);
+        ALDM_CHECK(st.s[j] < T, "%s: starts[%d]=%d must lie below T=%d", name, j, st.s[j], T);
+        ALDM_CHECK(st.s[j] - st.s[j - 1] <= Tw, "%s: gap of %d frames between starts[%d] and starts[%d] exceeds Tw=%d: frames "
+                   "without a window", name, st.s[j] - st.s[j - 1], j - 1, j, Tw);
+    }
+    ALDM_CHECK(T - st.s[W - 1] <= Tw, "%s: gap of %d frames between starts[%d] and the wrap to frame 0 exceeds Tw=%d: frames "
+               "without a window", name, T - st.s[W - 1], W - 1, Tw);
+    ALDM_CHECK((int64_t)W * B * C * Tw * F <= (1ll << 40), "%s: %lld window elements", name, (long long)W * B * C * Tw * F);
+    return 0;
+}
+
 // the host-side checks the entries share: the shape, and starts that tile [0, T) with windows of Tw
 static int window_args_ok(const char* name, const aldm_window_starts& st, int B, int W, int C, int T, int Tw, int F) {
     ALDM_CHECK(B > 0 && C > 0 && F > 0 && Tw > 0 && T >= Tw, "%s: bad shape (B=%d, C=%d, T=%d, Tw=%d, F=%d)", name, B, C, T, Tw, F);
@@ -200,5 +319,72 @@ extern "C" int aldm_window_merge(const float* win, const float* wn, float* out, 
                            C, T, Tw, F, n_out);
     }
     ALDM_LAUNCH_CHECK("aldm_window_merge");
+    return 0;
+}
+
+// ---- the ring entries (ABI v20): the argument lists of their linear siblings ------------------------------------------------------
+extern "C" int aldm_window_gather_ring(const float* x, float* win, aldm_window_starts starts, int B, int W, int C, int T, int Tw,
+                                       int F, void* stream) {
+    ALDM_CHECK(x && win, "aldm_window_gather_ring: null pointer");
+    if (window_ring_args_ok("aldm_window_gather_ring", starts, B, W, C, T, Tw, F) != 0) return -1;
+    const int64_t n_x = (int64_t)B * C * T * F, n_w = (int64_t)W * B * C * Tw * F;
+    ALDM_CHECK(!spans_overlap(x, n_x, win, n_w), "aldm_window_gather_ring: win overlaps x");
+    const int64_t per_window = (int64_t)B * C * Tw * F;
+    const dim3 block(256);
+    if (F % 4 == 0 && (((uintptr_t)x | (uintptr_t)win) & 15) == 0) {
+        const dim3 grid(win_blocks(per_window / 4), W);
+        hipLaunchKernelGGL(window_gather_ring_kernel<4>, grid, block, 0, (hipStream_t)stream, x, win, starts, T, Tw, F,
+                           (int64_t)Tw * F / 4, per_window / 4);
+    } else {
+        const dim3 grid(win_blocks(per_window), W);
+        hipLaunchKernelGGL(window_gather_ring_kernel<1>, grid, block, 0, (hipStream_t)stream, x, win, starts, T, Tw, F,
+                           (int64_t)Tw * F, per_window);
+    }
+    ALDM_LAUNCH_CHECK("aldm_window_gather_ring");
+    return 0;
+}
+
+extern "C" int aldm_window_blend_gather_ring(float* x, const float* x0, const float* qnoise, const float* mask,
+                                             const float* blend_coef, const int* step_idx, int q_rows, int coef_rows, float* win,
+                                             aldm_window_starts starts, int B, int W, int C, int T, int Tw, int F, void* stream) {
+    ALDM_CHECK(x && x0 && qnoise && mask && blend_coef && win, "aldm_window_blend_gather_ring: null pointer");
+    if (window_ring_args_ok("aldm_window_blend_gather_ring", starts, B, W, C, T, Tw, F) != 0) return -1;
+    ALDM_CHECK(q_rows >= 1 && coef_rows >= 1, "aldm_window_blend_gather_ring: q_rows=%d and coef_rows=%d must be >= 1", q_rows,
+               coef_rows);
+    const int64_t n_x = (int64_t)B * C * T * F, n_w = (int64_t)W * B * C * Tw * F, n_q = (int64_t)q_rows * n_x;
+    ALDM_CHECK(!spans_overlap(win, n_w, x, n_x) && !spans_overlap(win, n_w, x0, n_x) && !spans_overlap(win, n_w, qnoise, n_q) &&
+               !spans_overlap(win, n_w, mask, n_x), "aldm_window_blend_gather_ring: win overlaps x, x0, qnoise or mask");
+    ALDM_CHECK(!spans_overlap(x, n_x, x0, n_x) && !spans_overlap(x, n_x, qnoise, n_q) && !spans_overlap(x, n_x, mask, n_x),
+               "aldm_window_blend_gather_ring: x overlaps x0, qnoise or mask");
+    const dim3 block(256);
+    if (F % 4 == 0 &&
+        (((uintptr_t)x | (uintptr_t)x0 | (uintptr_t)qnoise | (uintptr_t)mask | (uintptr_t)win) & 15) == 0) {
+        hipLaunchKernelGGL(window_blend_gather_ring_kernel<4>, dim3(win_blocks(n_x / 4)), block, 0, (hipStream_t)stream, x, x0,
+                           qnoise, mask, blend_coef, step_idx, q_rows, coef_rows, win, starts, B, W, C, T, Tw, F, n_x / 4);
+    } else {
+        hipLaunchKernelGGL(window_blend_gather_ring_kernel<1>, dim3(win_blocks(n_x)), block, 0, (hipStream_t)stream, x, x0, qnoise,
+                           mask, blend_coef, step_idx, q_rows, coef_rows, win, starts, B, W, C, T, Tw, F, n_x);
+    }
+    ALDM_LAUNCH_CHECK("aldm_window_blend_gather_ring");
+    return 0;
+}
+
+extern "C" int aldm_window_merge_ring(const float* win, const float* wn, float* out, aldm_window_starts starts, int H, int B, int W,
+                                      int C, int T, int Tw, int F, void* stream) {
+    ALDM_CHECK(win && wn && out, "aldm_window_merge_ring: null pointer");
+    ALDM_CHECK(H == 1 || H == 2, "aldm_window_merge_ring: H=%d: 1, or 2 for the [uncond ; cond] pair", H);
+    if (window_ring_args_ok("aldm_window_merge_ring", starts, B, W, C, T, Tw, F) != 0) return -1;
+    const int64_t n_out = (int64_t)H * B * C * T * F, n_w = (int64_t)H * W * B * C * Tw * F;
+    ALDM_CHECK(!spans_overlap(out, n_out, win, n_w) && !spans_overlap(out, n_out, wn, (int64_t)W * Tw),
+               "aldm_window_merge_ring: out overlaps win or wn");
+    const dim3 block(256);
+    if (F % 4 == 0 && (((uintptr_t)win | (uintptr_t)out) & 15) == 0) {
+        hipLaunchKernelGGL(window_merge_ring_kernel<4>, dim3(win_blocks(n_out / 4)), block, 0, (hipStream_t)stream, win, wn, out,
+                           starts, B, W, C, T, Tw, F, n_out / 4);
+    } else {
+        hipLaunchKernelGGL(window_merge_ring_kernel<1>, dim3(win_blocks(n_out)), block, 0, (hipStream_t)stream, win, wn, out, starts,
+                           B, W, C, T, Tw, F, n_out);
+    }
+    ALDM_LAUNCH_CHECK("aldm_window_merge_ring");
     return 0;
 }

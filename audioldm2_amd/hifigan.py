@@ -51,6 +51,30 @@ def _get_padding(kernel_size, dilation=1):
     return int((kernel_size * dilation - dilation) / 2)
 
 
+def reach_frames(h) -> int:
+    """Pure host: an upper bound, in mel frames, of how far to one side an output sample of the generator built from the config
+    `h` depends on its input mel — the circular padding a periodic mel needs for the vocoder's output over one period to be that of
+    the endlessly repeated mel (seamless loops).  Layer by layer, each layer's one-sided reach in its own samples
+    divided by the upsampling accumulated so far (c_i = u_0 * ... * u_i samples per mel frame behind stage i):
+      conv_pre, kernel 7                                                   3 frames
+      stage i's transposed convolution, kernel k_i                         at most (k_i - 1) / c_i
+      stage i's ResBlocks run in parallel; the one with the largest kernel k reaches furthest: per dilation d a conv of reach
+      d*(k-1)/2 followed by one of reach (k-1)/2                           (sum_d d*(k-1)/2 + len(d)*(k-1)/2) / c_i
+      conv_post, kernel 7                                                  3 / c_last
+    summed exactly (fractions) and rounded up.  Derived from the config, not tuned: 25 frames for the 16 kHz generator, 24 for
+    the 48 kHz one."""
+    from fractions import Fraction
+    reach = Fraction(3)
+    c = 1
+    for u, k in zip(h["upsample_rates"], h["upsample_kernel_sizes"]):
+        c *= int(u)
+        reach += Fraction(int(k) - 1, c)
+        reach += max(Fraction((sum(int(d) for d in ds) + len(ds)) * ((int(kr) - 1) // 2), c)
+                     for kr, ds in zip(h["resblock_kernel_sizes"], h["resblock_dilation_sizes"]))
+    reach += Fraction(3, c)
+    return int(-(-reach.numerator // reach.denominator))
+
+
 class ResBlock(nn.Module):
     """hifigan/models.py:20-103 parameter holder (convs1: dilated, convs2: dilation 1)."""
 

@@ -1616,6 +1616,12 @@ def _window_starts(plan) -> "_l.WindowStarts":
     return st
 
 
+def _window_entry(plan, name: str):
+    """The C entry of a window launch: `name`, or its wrap-around form `name`_ring for a ring plan (windows.window_plan(...,
+    ring=True); the argument lists are the same)."""
+    return getattr(_l.load(), name + "_ring" if getattr(plan, "ring", False) else name)
+
+
 def _no_overlap(out: torch.Tensor, what: str, others) -> None:
     a0, a1 = out.data_ptr(), out.data_ptr() + 4 * out.numel()
     for t, name in others:
@@ -1626,7 +1632,8 @@ def _no_overlap(out: torch.Tensor, what: str, others) -> None:
 
 def window_gather(x: torch.Tensor, plan, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The windows of a long tensor (aldm_window_gather): x [B, C, T, F] -> [W*B, C, Tw, F], row j*B + b = x[b, :, s_j:s_j + Tw]
-    (window-major), a bit-exact copy.  `plan`: windows.window_plan(T, Tw, hop); `out`: write into this (it may not overlap x)."""
+    (window-major), a bit-exact copy.  `plan`: windows.window_plan(T, Tw, hop); `out`: write into this (it may not overlap x).  A
+    ring plan (plan.ring) takes aldm_window_gather_ring: row j*B + b = the frames (s_j + p) mod T, p in [0, Tw)."""
     _chk(x, "window_gather.x")
     if x.dim() != 4 or x.shape[2] != plan.T or x.numel() == 0:
         raise RuntimeError(f"window_gather: x must be [B, C, T={plan.T}, F], got {tuple(x.shape)}")
@@ -1638,7 +1645,7 @@ def window_gather(x: torch.Tensor, plan, out: Optional[torch.Tensor] = None) -> 
     if tuple(out.shape) != shape:
         raise RuntimeError(f"window_gather.out: expected {shape}, got {tuple(out.shape)}")
     _no_overlap(out, "window_gather.out", [(x, "x")])
-    _l.check(_l.load().aldm_window_gather(x.data_ptr(), out.data_ptr(), _window_starts(plan), B, plan.W, C, T, plan.Tw, F,
+    _l.check(_window_entry(plan, "aldm_window_gather")(x.data_ptr(), out.data_ptr(), _window_starts(plan), B, plan.W, C, T, plan.Tw, F,
                                           _stream()), "window_gather")
     return out
 
@@ -1649,7 +1656,8 @@ def window_blend_gather(x: torch.Tensor, x0: torch.Tensor, qnoise: torch.Tensor,
     x = (sa*x0 + so*qn)*mask + (1 - mask)*x, then the windows of the blended x -> [W*B, C, Tw, F] — bitwise inpaint_blend followed by
     window_gather.  x, x0, mask [B, C, T, F]; qnoise [q_rows, B, C, T, F], or [B, C, T, F] for one row; blend_coef [coef_rows, 2] =
     {sa, so}, or [2] for one row; step_idx (int32 [1] on the device, None: 0) selects row min(step_idx, rows - 1) of each table on
-    the device.  `out`: write the windows into this.  out may overlap no operand, x none of x0, qnoise, mask."""
+    the device.  `out`: write the windows into this.  out may overlap no operand, x none of x0, qnoise, mask.  A ring plan
+    (plan.ring) takes aldm_window_blend_gather_ring: the same blend, the window copies at their wrapped positions."""
     for t, n in ((x, "x"), (x0, "x0"), (qnoise, "qnoise"), (mask, "mask"), (blend_coef, "blend_coef")):
         _chk(t, "window_blend_gather." + n)
     if x.dim() != 4 or x.shape[2] != plan.T or x.numel() == 0:
@@ -1679,7 +1687,7 @@ def window_blend_gather(x: torch.Tensor, x0: torch.Tensor, qnoise: torch.Tensor,
     others = [(x0, "x0"), (qnoise, "qnoise"), (mask, "mask")]
     _no_overlap(out, "window_blend_gather.out", [(x, "x")] + others + [(blend_coef, "blend_coef")])
     _no_overlap(x, "window_blend_gather.x", others + [(blend_coef, "blend_coef")])
-    _l.check(_l.load().aldm_window_blend_gather(x.data_ptr(), x0.data_ptr(), qnoise.data_ptr(), mask.data_ptr(),
+    _l.check(_window_entry(plan, "aldm_window_blend_gather")(x.data_ptr(), x0.data_ptr(), qnoise.data_ptr(), mask.data_ptr(),
                                                 blend_coef.data_ptr(), _p(step_idx), q_rows, coef_rows, out.data_ptr(),
                                                 _window_starts(plan), B, plan.W, C, T, plan.Tw, F, _stream()),
              "window_blend_gather")
@@ -1690,7 +1698,8 @@ def window_merge(win: torch.Tensor, plan, out: Optional[torch.Tensor] = None) ->
     """The tapered, normalised overlap-add of window-wise tensors (aldm_window_merge): win [W*B, C, Tw, F] -> [B, C, T, F], or
     win [2, W*B, C, Tw, F] (the [uncond ; cond] pair of a guided UNet pass) -> [2, B, C, T, F]; rows window-major as
     window_gather writes them.  Per output element the covering windows in ascending order, wn*e first, then one fmaf each, in
-    fp32: bitwise reproducible.  `out`: write into this (it may not overlap win)."""
+    fp32: bitwise reproducible.  `out`: write into this (it may not overlap win).  A ring plan (plan.ring) takes
+    aldm_window_merge_ring: the overlap-add round the circle of plan.T frames."""
     from .windows import device_weights
     _chk(win, "window_merge.win")
     if win.dim() not in (4, 5) or (win.dim() == 5 and win.shape[0] != 2) or win.shape[-2] != plan.Tw or win.numel() == 0 \
@@ -1707,7 +1716,7 @@ def window_merge(win: torch.Tensor, plan, out: Optional[torch.Tensor] = None) ->
         raise RuntimeError(f"window_merge.out: expected {shape}, got {tuple(out.shape)}")
     wn = device_weights(plan, win.device)
     _no_overlap(out, "window_merge.out", [(win, "win"), (wn, "wn")])
-    _l.check(_l.load().aldm_window_merge(win.data_ptr(), wn.data_ptr(), out.data_ptr(), _window_starts(plan), H, B, plan.W, C,
+    _l.check(_window_entry(plan, "aldm_window_merge")(win.data_ptr(), wn.data_ptr(), out.data_ptr(), _window_starts(plan), H, B, plan.W, C,
                                          plan.T, plan.Tw, F, _stream()), "window_merge")
     return out
 

@@ -1006,10 +1006,12 @@ class LatentDiffusion(nn.Module):
                                      **_sample_log_keywords(sampler, guidance_rescale, t_enc))
         return _waveform_of(self, samples, batch, text, n_gen, B0)
 
-    def long_form_plans(self, latent_t_size, hop=None):
+    def long_form_plans(self, latent_t_size, hop=None, ring=False):
         """Pure host: (latent-domain plan, mel-domain plan) of a long clip of `latent_t_size` latent frames through windows of
         `self.latent_t_size` frames, `hop` (default 3*Tw//4) apart — windows.window_plan; the mel plan is the latent one scaled by
-        the VAE's time factor.  ValueError for a length that is no multiple of 8 or shorter than the window, and for a bad hop."""
+        the VAE's time factor.  `ring=True`: the ring plans of a seamless loop — at most `hop` apart, spread evenly
+        round the circle; latent_t_size == Tw is a legal ring, hop == Tw is not.  ValueError for a length that is no multiple of 8
+        or shorter than the window, and for a bad hop."""
         from .windows import window_plan
         self.check_latent_t(latent_t_size)
         Tw = self.latent_t_size
@@ -1019,12 +1021,13 @@ class LatentDiffusion(nn.Module):
                              "frames: use generate_batch / text_to_audio for a clip of at most the trained length")
         hop = 3 * Tw // 4 if hop is None else hop
         f = 2 ** (self.first_stage_model.encoder.num_resolutions - 1)
-        return window_plan(int(latent_t_size), Tw, hop), window_plan(int(latent_t_size), Tw, hop, scale=f)
+        return (window_plan(int(latent_t_size), Tw, hop, ring=bool(ring)),
+                window_plan(int(latent_t_size), Tw, hop, scale=f, ring=bool(ring)))
 
     @torch.no_grad()
     def generate_batch_long(self, batch, latent_t_size, hop=None, ddim_steps=200, ddim_eta=1.0, unconditional_guidance_scale=1.0,
                             unconditional_conditioning=None, use_plms=False, sampler=None, negative_prompt=None,
-                            guidance_rescale=0.0, n_gen=1, shard=None):
+                            guidance_rescale=0.0, n_gen=1, shard=None, loop=False):
         """Long-form text-to-audio by windowed diffusion (MultiDiffusion, Bar-Tal et al. 2023): ONE long latent of
         `latent_t_size` frames; at every step the UNet runs on overlapping windows of `self.latent_t_size` frames — the trained
         length, `hop` frames apart (default 3*Tw//4) — in one pass over W*b rows, the windows' outputs are fused by a tapered,
@@ -1034,14 +1037,24 @@ class LatentDiffusion(nn.Module):
         trained shape.  All windows share one conditioning: right for ambience, textures and music, wrong for a transcription
         that should advance through the clip.  `sampler`, `negative_prompt` and `guidance_rescale` as in generate_batch.
 
+        `loop=True`: a clip that loops without a seam.  Sampling runs on the RING plan of the same numbers
+        (long_form_plans(..., ring=True)): the window starts are spread round a circle of `latent_t_size` frames and windows wrap
+        from the last frame to the first, so at every step the junction of end and start lies inside a window like every other
+        frame boundary (ops.window_gather / ops.window_merge dispatch to the wrap-around kernels on plan.ring; the step graph is
+        the linear one's but for those nodes).  The tail is the ring's too: a ring gather of the final latent, the VAE on the
+        windows, a ring merge of the mels — a periodic mel by construction — and the vocoder over that mel circularly padded by
+        hifigan.reach_frames(config) mel frames on both sides (one torch.cat per job), its output cut back to the clip.
+        latent_t_size == the trained length is legal here (two half-shifted windows, one across the junction), hop == Tw is not.
+
         Refused before any draw or GPU work: ddim_steps=None (the ancestral sampler has no windowed form), n_gen != 1 (the CLAP
         re-ranker scores clips of the trained length), shard=, a length that is no multiple of 8 or shorter than the window, more
-        than 32 windows.
+        than 32 windows; with loop=True also a hop of the whole window (no overlap: nothing would denoise across the junction).
 
         Host-generator order (RNG contract R): (R1) randn(B0, C, h, w) of the batch's mel, drawn and discarded
         exactly as generate_batch does; (R1b) the rand(1) of _cfg_dropout_draw on every call but an object's first; the
         conditioners' draws (twice with a negative prompt); randn(B0, C, latent_t_size, F), the long x_T; the sampler's per-step
-        draws at that long shape (DDIM one per step, PLMS one per step and one more in its first, DPM-Solver++ none)."""
+        draws at that long shape (DDIM one per step, PLMS one per step and one more in its first, DPM-Solver++ none).  loop=True
+        draws exactly what the linear job draws, in the same order: a ring changes which frames a window sees, not a draw."""
         if shard is not None:
             raise ValueError("generate_batch_long: shard= is not supported on this path")
         if ddim_steps is None:
@@ -1053,7 +1066,7 @@ class LatentDiffusion(nn.Module):
         kw = {} if negative_prompt is None else {"negative_prompt": negative_prompt}
         neg_batch, guidance_rescale = _guidance_kwargs(dict(kw, guidance_rescale=guidance_rescale), unconditional_guidance_scale,
                                                        batch, ddim_steps)
-        plan, mel_plan = self.long_form_plans(latent_t_size, hop)
+        plan, mel_plan = self.long_form_plans(latent_t_size, hop, ring=loop)
         fb = batch["log_mel_spec"] if self.first_stage_key == "fbank" else batch[self.first_stage_key]
         B0 = fb.shape[0]
         f = 2 ** (self.first_stage_model.encoder.num_resolutions - 1)
@@ -1070,10 +1083,20 @@ class LatentDiffusion(nn.Module):
 
     def _long_tail(self, samples, plan, mel_plan, batch):
         """The tail of a long-form job: the VAE at its trained shape on the W*B0 windows of the final latent, the mels cross-faded
-        on the scaled plan, one vocoder pass, the cut."""
+        on the scaled plan, one vocoder pass, the cut.  On ring plans (a loop) gather and merge wrap, so the mel is periodic, and
+        the vocoder sees it circularly padded by P = hifigan.reach_frames(config) mel frames on both sides — P bounds how far an
+        output sample looks into the mel, so the samples [P*h, (P + T_mel)*h) kept are those of the endlessly repeated mel."""
         mel_w = self.decode_first_stage_cl(ops.window_gather(samples, plan))   # [W*B0, Tw*f, F_mel, 1] channels-last
         mel = ops.window_merge(mel_w.view(mel_w.shape[0], 1, mel_w.shape[1], mel_w.shape[2]), mel_plan)   # [B0, 1, T*f, F_mel]
         self.last_long_latent, self.last_long_mel = samples, mel
+        if getattr(mel_plan, "ring", False):
+            from .hifigan import reach_frames
+            h = int(np.prod(self.first_stage_model.vocoder.h.upsample_rates))
+            P, T_mel = reach_frames(self.first_stage_model.vocoder.h), mel.shape[-2]
+            assert P <= T_mel, f"a loop of {T_mel} mel frames is shorter than the vocoder's reach of {P}"   # trained windows: >= 512
+            padded = torch.cat([mel[:, :, T_mel - P:], mel, mel[:, :, :P]], dim=2)   # once per job
+            waveform = self.mel_spectrogram_to_waveform(padded, savepath="", bs=None, name=batch.get("fname"), save=False)
+            return np.ascontiguousarray(waveform[..., P * h:(P + T_mel) * h])
         waveform = self.mel_spectrogram_to_waveform(mel, savepath="", bs=None, name=batch.get("fname"), save=False)
         # a long clip has exactly one vocoder hop per mel frame: the few samples the vocoder's first transposed convolution
         # appends (kernel 16 at stride 5: 32 of them at 16 kHz) are cut
@@ -1109,7 +1132,7 @@ class LatentDiffusion(nn.Module):
     @torch.no_grad()
     def generate_batch_long_from_audio(self, batch, latent_t_size, keep, hop=None, ddim_steps=200, ddim_eta=1.0,
                                        unconditional_guidance_scale=1.0, use_plms=False, sampler=None, negative_prompt=None,
-                                       guidance_rescale=0.0, n_gen=1, shard=None):
+                                       guidance_rescale=0.0, n_gen=1, shard=None, loop=False):
         """Continuation and inpainting of long clips: generate_batch_long around a source.  `batch["log_mel_spec"]`
         is the long mel [B0, latent_t_size*f, F_mel] of the source; `keep` lists the half-open latent-frame intervals [a, b) to
         keep (windows.keep_mask); everything else is generated under the prompt.  The source is encoded window by window
@@ -1119,6 +1142,11 @@ class LatentDiffusion(nn.Module):
 
         As in the reference's inpainting (ddim.py:226-231) the final latent is NOT pasted over with the source: the kept region
         is what the last blend (at the lowest noise level) and the last step leave — close to the source, not bitwise it.
+
+        `loop=True`: a continuation whose end runs back into the source's beginning ("make my 8 seconds loop by generating a
+        4-second bridge").  The source is encoded on the LINEAR plans exactly as without it — a recording is not
+        periodic — sampling runs on the ring plan with that source (windows.with_source keeps the flag) and the tail is
+        generate_batch_long's ring tail.  `keep` means what it means without it; the draws and their order do not change.
 
         Refused before any draw or GPU work: ddim_steps=None, n_gen != 1, shard=, bad lengths or hops (long_form_plans), a bad
         `keep`, a mel whose length is not latent_t_size*f.
@@ -1140,6 +1168,7 @@ class LatentDiffusion(nn.Module):
         neg_batch, guidance_rescale = _guidance_kwargs(dict(kw, guidance_rescale=guidance_rescale), unconditional_guidance_scale,
                                                        batch, ddim_steps)
         plan, mel_plan = self.long_form_plans(latent_t_size, hop)
+        ring_plans = self.long_form_plans(latent_t_size, hop, ring=True) if loop else None   # refuses a bad ring before any draw
         mask_t = keep_mask(plan.T, keep)
         fb = batch["log_mel_spec"] if self.first_stage_key == "fbank" else batch[self.first_stage_key]
         f = 2 ** (self.first_stage_model.encoder.num_resolutions - 1)
@@ -1153,6 +1182,8 @@ class LatentDiffusion(nn.Module):
         unconditional_conditioning = _unconditional_half(self, neg_batch, 1, B0, unconditional_guidance_scale)
         z = self.encode_long(fb.unsqueeze(1).float().contiguous().to(self.device), plan, mel_plan, n_post.to(self.device))
         self.last_long_source = z
+        if loop:   # the source was encoded on the linear plans; sampling and the tail run on the ring
+            plan, mel_plan = ring_plans
         samples, _ = self.sample_log(cond=c, batch_size=B0, x_T=None, ddim=True, ddim_steps=ddim_steps, eta=ddim_eta,
                                      unconditional_guidance_scale=unconditional_guidance_scale,
                                      unconditional_conditioning=unconditional_conditioning, use_plms=use_plms,
@@ -1411,24 +1442,26 @@ def text_to_audio(latent_diffusion, text, transcription="", seed=42, ddim_steps=
 
 
 def text_to_audio_long(latent_diffusion, text, duration, overlap=2.5, transcription="", seed=42, ddim_steps=200, guidance_scale=3.5,
-                       sampler=None, negative_prompt=None, guidance_rescale=0.0):
+                       sampler=None, negative_prompt=None, guidance_rescale=0.0, loop=False):
     """Long-form text-to-audio: a clip of `duration` seconds — longer than the model's trained length — by windowed diffusion
     (LatentDiffusion.generate_batch_long): the UNet and the VAE work on windows of the model's `latent_t_size` frames that overlap
     by `overlap` seconds, fused at every step.  latent_t_size = int(duration * latent_t_per_second) must be a multiple of 8 and
     at least the window; hop = Tw - round(overlap * latent_t_per_second) must lie in [1, Tw]; both are refused before any GPU
     work.  One candidate per prompt (no CLAP re-ranking of long clips); all windows share the prompt's conditioning, so a
     transcription does not advance through the clip.  `sampler`, `negative_prompt`, `guidance_rescale` as in text_to_audio.  The
-    model's own latent_t_size is not changed.  Returns np.float32 [1, 1, samples]."""
+    model's own latent_t_size is not changed.  `loop=True`: a clip whose last sample runs into its first — windowed diffusion
+    on a ring (generate_batch_long(..., loop=True)); `duration` may then equal the trained length, and `overlap` must be
+    positive (a ring without overlap has nothing across its junction).  Returns np.float32 [1, 1, samples]."""
     sampler_kw = _sampler_kwargs(sampler, negative_prompt, guidance_rescale)
     per_second = float(latent_diffusion.latent_t_per_second)
     latent_t = int(duration * per_second)
     hop = latent_diffusion.latent_t_size - int(round(overlap * per_second))
-    latent_diffusion.long_form_plans(latent_t, hop)   # refuse before any GPU work
+    latent_diffusion.long_form_plans(latent_t, hop, ring=loop)   # refuse before any GPU work
     seed_everything(int(seed))
     batch = make_batch_for_text_to_audio(text, transcription=transcription, batchsize=1)
     with torch.no_grad():
         return latent_diffusion.generate_batch_long(batch, latent_t, hop=hop, unconditional_guidance_scale=guidance_scale,
-                                                    ddim_steps=ddim_steps, **sampler_kw)
+                                                    ddim_steps=ddim_steps, loop=loop, **sampler_kw)
 
 
 def _source_seconds(source):
@@ -1458,7 +1491,7 @@ def keep_frames(keep, per_second, latent_t):
 
 
 def extend_audio(latent_diffusion, text, original_audio_file_path, duration, keep=None, overlap=2.5, transcription="", seed=42,
-                 ddim_steps=200, guidance_scale=3.5, sampler=None, negative_prompt=None, guidance_rescale=0.0):
+                 ddim_steps=200, guidance_scale=3.5, sampler=None, negative_prompt=None, guidance_rescale=0.0, loop=False):
     """Continue or inpaint a long clip: a clip of `duration` seconds — longer than the model's trained length — that keeps parts
     of the recording `original_audio_file_path` (a path, or a 1-D float waveform at 16 kHz; zero-padded or cut to `duration`) and
     generates the rest under the prompt `text` by windowed diffusion (LatentDiffusion.generate_batch_long_from_audio).  `keep`
@@ -1469,6 +1502,8 @@ def extend_audio(latent_diffusion, text, original_audio_file_path, duration, kee
     `guidance_rescale` as in text_to_audio_long; the front end is audio_to_audio's (wav_to_fbank, the 16 kHz TacotronSTFT): a
     model whose first stage is not 16 kHz / 64 mel bins is refused.  Everything is refused before any draw or GPU work.  The kept
     region is not pasted back at the end (see generate_batch_long_from_audio).  The model's own latent_t_size is not changed.
+    `loop=True`: the generated part runs back into the source's beginning, so the whole clip loops ("make my 8 seconds loop by
+    generating a 4-second bridge": duration=12, the default keep); `overlap` must then be positive.
     Returns np.float32 [1, 1, samples]."""
     from .stft import TacotronSTFT
     from .windows import keep_mask
@@ -1481,6 +1516,8 @@ def extend_audio(latent_diffusion, text, original_audio_file_path, duration, kee
     latent_t = int(duration * per_second)
     hop = latent_diffusion.latent_t_size - int(round(overlap * per_second))
     latent_diffusion.long_form_plans(latent_t, hop)   # refuse before any GPU work
+    if loop:
+        latent_diffusion.long_form_plans(latent_t, hop, ring=True)
     f = 2 ** (latent_diffusion.first_stage_model.encoder.num_resolutions - 1)
     mel_bins = int(latent_diffusion.latent_f_size) * f
     if int(latent_diffusion.sampling_rate) != 16000 or mel_bins != 64:
@@ -1498,7 +1535,7 @@ def extend_audio(latent_diffusion, text, original_audio_file_path, duration, kee
     with torch.no_grad():
         return latent_diffusion.generate_batch_long_from_audio(batch, latent_t, frames, hop=hop,
                                                                unconditional_guidance_scale=guidance_scale,
-                                                               ddim_steps=ddim_steps, **sampler_kw)
+                                                               ddim_steps=ddim_steps, loop=loop, **sampler_kw)
 
 
 def audio_to_audio(latent_diffusion, text, original_audio_file_path, strength=0.5, transcription="", seed=42,

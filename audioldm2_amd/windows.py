@@ -24,7 +24,7 @@ def _check_int(v, name):
     return int(v)
 
 
-def window_plan(T, Tw, hop, scale=1):
+def window_plan(T, Tw, hop, scale=1, ring=False):
     """The plan of windows of `Tw` frames, `hop` frames apart, over `T` frames -> an object with
 
       starts  s_j = j*hop while s_j + Tw < T, then a final T - Tw: s_0 = 0, the last window ends at T, consecutive starts differ
@@ -38,8 +38,16 @@ def window_plan(T, Tw, hop, scale=1):
     `scale` multiplies T, Tw and hop (and so the starts) first: the mel-domain plan of a latent-domain one (x4 for the 16 kHz VAE);
     its taper is the same formula on the scaled numbers.
 
-    ValueError: T or Tw not a positive multiple of 8 (the UNet's three stride-2 levels), T < Tw, hop not an integer in [1, Tw],
-    more than 32 windows."""
+    `ring=True`: a ring plan (seamless loops).  The T frames are a circle: W = ceil(T / hop) windows start at
+    s_j = (j*T) // W — computed on the unscaled numbers, then scaled, so a mel plan's starts are exactly `scale` times the latent
+    plan's — and window j covers the frames (s_j + p) mod T, p in [0, Tw): it may wrap from frame T-1 to frame 0, and the junction of
+    end and start lies inside a window like every other frame boundary.  The gaps s_{j+1} - s_j (the last one T - s_{W-1}) are
+    floor(T/W) or ceil(T/W), hence <= hop; the taper is the same formula with ramp = Tw - (the largest gap) >= 1, normalised by the
+    circular sum of the tapers over every frame.  hop must lie in [1, Tw-1]; T == Tw is a legal ring (two half-shifted windows).
+    The returned object carries `ring` (False for a linear plan).
+
+    ValueError: T or Tw not a positive multiple of 8 (the UNet's three stride-2 levels), T < Tw, hop not an integer in [1, Tw]
+    ([1, Tw-1] for a ring), more than 32 windows."""
     T, Tw, hop, scale = _check_int(T, "T"), _check_int(Tw, "Tw"), _check_int(hop, "hop"), _check_int(scale, "scale")
     for v, name in ((T, "T"), (Tw, "Tw")):
         if v <= 0 or v % 8 != 0:
@@ -50,6 +58,8 @@ def window_plan(T, Tw, hop, scale=1):
         raise ValueError(f"window_plan: hop must lie in [1, Tw={Tw}], got {hop}")
     if scale < 1:
         raise ValueError(f"window_plan: scale must be a positive integer, got {scale}")
+    if ring:
+        return _ring_plan(T, Tw, hop, scale)
     T, Tw, hop = T * scale, Tw * scale, hop * scale
     starts = []
     s = 0
@@ -71,13 +81,42 @@ def window_plan(T, Tw, hop, scale=1):
     wn = np.stack([w / norm[s:s + Tw] for s in starts])
     # one window over a frame: w / w — exactly 1 in fp64 already; stated here because the kernels' bit-exact cases rest on it
     assert all(np.all(wn[j][count[s:s + Tw] == 1] == 1.0) for j, s in enumerate(starts))
-    return SimpleNamespace(T=T, Tw=Tw, hop=hop, scale=scale, W=W, starts=tuple(starts), cover=int(count.max()),
+    return SimpleNamespace(T=T, Tw=Tw, hop=hop, scale=scale, W=W, starts=tuple(starts), cover=int(count.max()), ring=False,
+                           wn=torch.from_numpy(wn.astype(np.float32)).contiguous())
+
+
+def _ring_plan(T, Tw, hop, scale):
+    """window_plan's ring form, on the checked, unscaled numbers."""
+    if hop == Tw:
+        raise ValueError(f"window_plan: a ring needs hop < Tw={Tw}: with hop == Tw the windows do not overlap, the junction of the "
+                         "clip's end and start lies between two windows and nothing denoises across it")
+    W = -(-T // hop)
+    if W > MAX_WINDOWS:
+        raise ValueError(f"window_plan: a ring of T={T}, Tw={Tw}, hop={hop} needs more than {MAX_WINDOWS} windows")
+    starts = [((j * T) // W) * scale for j in range(W)]
+    T, Tw, hop = T * scale, Tw * scale, hop * scale
+    gaps = [b - a for a, b in zip(starts, starts[1:] + [T])]
+    ramp = Tw - max(gaps)
+    assert W >= 2 and starts[0] == 0 and min(gaps) >= 1 and max(gaps) <= hop and ramp >= 1
+    p = np.arange(Tw, dtype=np.float64)
+    w = np.minimum(1.0, np.minimum((p + 1.0) / (ramp + 1.0), (Tw - p) / (ramp + 1.0)))
+    frames = [(s + np.arange(Tw)) % T for s in starts]     # Tw <= T: a window covers no frame twice
+    norm = np.zeros(T, dtype=np.float64)
+    count = np.zeros(T, dtype=np.int64)
+    for fr in frames:
+        norm[fr] += w
+        count[fr] += 1
+    wn = np.stack([w / norm[fr] for fr in frames])
+    # one window over a frame: w / w, exactly 1 in fp64 already (the merge kernel's bit-exact frames rest on it)
+    assert int(count.min()) >= 1 and all(np.all(wn[j][count[fr] == 1] == 1.0) for j, fr in enumerate(frames))
+    return SimpleNamespace(T=T, Tw=Tw, hop=hop, scale=scale, W=W, starts=tuple(starts), cover=int(count.max()), ring=True,
                            wn=torch.from_numpy(wn.astype(np.float32)).contiguous())
 
 
 def plan_key(plan):
-    """What identifies a plan's launch sequence (the starts are kernel arguments captured with a step graph)."""
-    return (plan.T, plan.Tw, tuple(plan.starts))
+    """What identifies a plan's launch sequence (the starts are kernel arguments captured with a step graph; a ring plan launches
+    the wrap-around kernels, so a ring and a linear plan never share a step graph)."""
+    return (plan.T, plan.Tw, tuple(plan.starts), bool(getattr(plan, "ring", False)))
 
 
 def keep_mask(T, intervals):
@@ -110,8 +149,8 @@ def keep_mask(T, intervals):
 
 def with_source(plan, x0, mask):
     """`plan` with a source to keep (continuation and inpainting of long clips): a plan object with the same T, Tw,
-    starts and wn — and so the same plan_key — that additionally carries `x0` [b, C, T, F] (the source's scaled latent) and `mask`
-    (broadcastable to x0's shape; 1 = keep the source, 0 = generate; a [T] vector, as keep_mask returns it, is taken along the time
+    starts, ring flag and wn — and so the same plan_key — that additionally carries `x0` [b, C, T, F] (the source's scaled latent)
+    and `mask` (broadcastable to x0's shape; 1 = keep the source, 0 = generate; a [T] vector, as keep_mask returns it, is taken along the time
     axis).  A sampler given such a plan as `windows=` blends q_sample(x0, t) into the long latent in front of every step's gather
     (ops.window_blend_gather).  ValueError for shapes that do not fit plan.T."""
     if not torch.is_tensor(x0) or x0.dim() != 4 or x0.shape[2] != plan.T:

@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 /* ---- library / error ------------------------------------------------------------------ */
-int aldm_version(void);              /* ABI version (19), bumped on any struct / entry change */
+int aldm_version(void);              /* ABI version (20), bumped on any struct / entry change */
 const char* aldm_last_error(void);   /* message of the last failing call on this thread     */
 
 /* ---- activations usable as prologue (applied to the gathered input) or epilogue -------- */
@@ -588,6 +588,27 @@ int aldm_window_merge(const float* win, const float* wn, float* out, aldm_window
 int aldm_window_blend_gather(float* x, const float* x0, const float* qnoise, const float* mask, const float* blend_coef,
                              const int* step_idx, int q_rows, int coef_rows, float* win, aldm_window_starts starts, int B, int W,
                              int C, int T, int Tw, int F, void* stream);
+/* Ring plans (seamless loops), ABI v20: the T frames are a circle and window j covers the frames (s_j + p) mod T, p in
+ * [0, Tw), so a window may wrap from frame T-1 to frame 0 and the junction of end and start lies inside a window.  The three entries
+ * below are the wrap-around forms of aldm_window_gather, aldm_window_merge and aldm_window_blend_gather, with their siblings'
+ * argument lists, operation order and aliasing rules; the linear entries are unchanged.  The starts are checked on the host before
+ * the launch: n == W, 2 <= W <= ALDM_MAX_WINDOWS, s[0] == 0, strictly ascending and < T, every gap — the wrap gap T - s[W-1]
+ * included — <= Tw (every frame has a window), Tw <= T (no window covers a frame twice).  The wrap is along T: a 16-byte access
+ * along F never straddles it; it costs a compare and a subtract, no integer modulo.                                              */
+/* win[(j*B + b), c, p, f] = x[b, c, (s_j + p) mod T, f], a bit-exact copy: per (b, c) at most two contiguous spans of x. */
+int aldm_window_gather_ring(const float* x, float* win, aldm_window_starts starts, int B, int W, int C, int T, int Tw, int F,
+                            void* stream);
+/* out[h, b, c, t, f] = sum over the windows j, ascending, with p = (t - s_j) mod T < Tw, of wn[j, p] * win[h, j*B + b, c, p, f]:
+ * the first term a plain multiply, every later one one fmaf; H = 1 | 2; gather form, no atomics.  wn: the ring plan's weights,
+ * normalised by the circular sum of the tapers, so the output is periodic by construction.                                       */
+int aldm_window_merge_ring(const float* win, const float* wn, float* out, aldm_window_starts starts, int H, int B, int W, int C,
+                           int T, int Tw, int F, void* stream);
+/* aldm_window_blend_gather on a ring: in place x = (sa*x0 + so*qn)*m + (1 - m)*x, then win[(j*B + b), c, (t - s_j) mod T, f] = x
+ * for every window j that covers t.  Every window element has exactly one writer.  Bitwise aldm_inpaint_blend followed by
+ * aldm_window_gather_ring.                                                                                                        */
+int aldm_window_blend_gather_ring(float* x, const float* x0, const float* qnoise, const float* mask, const float* blend_coef,
+                                  const int* step_idx, int q_rows, int coef_rows, float* win, aldm_window_starts starts, int B,
+                                  int W, int C, int T, int Tw, int F, void* stream);
 /* generic y = alpha*a + beta*b (b may be NULL) */
 int aldm_axpby(const float* a, const float* b, float* y, float alpha, float beta, int64_t n,
                void* stream);
