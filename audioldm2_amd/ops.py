@@ -1116,6 +1116,100 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, *,
     return res
 
 
+# ---- folded cross-attention on a short context (csrc/xattn_fold.hip, ABI v21) ----
+# $ALDM_XATTN_FOLD: "0" off, unset / "1" on wherever the planner keeps it, or a comma list of widths C (e.g. "256,640"): on for
+# those widths only — the per-level A/B of docs/experiments_r1-r6.md §10.8.
+def _parse_xattn_fold(v):
+    v = "1" if v is None else str(v).strip()
+    if v in ("0", "False"):
+        return False
+    if v in ("", "1", "True"):
+        return True
+    return frozenset(int(t) for t in v.split(",") if t.strip())
+
+
+XATTN_FOLD = _parse_xattn_fold(os.environ.get("ALDM_XATTN_FOLD"))
+XATTN_FOLD_MAX_KEYS = 8
+
+
+def xattn_fold(on=None):
+    """In-process switch of the folded cross-attention (like igemm_epilogue_forms): False off, True on, a collection of widths C
+    on for those only; None leaves it.  Returns the previous setting.  Captured HIP graphs keep the path they were captured with."""
+    global XATTN_FOLD
+    prev = XATTN_FOLD
+    if on is not None:
+        XATTN_FOLD = on if isinstance(on, bool) else frozenset(int(c) for c in on)
+    return prev
+
+
+def xattn_fold_plan(B: int, L: int, C: int, heads: int, Lk: int) -> dict:
+    """Launch geometry of xattn_folded for a shape (aldm_xattn_fold_plan; host only): {"supported", "use", "tile_rows",
+    "col_splits", "waves", "blocks", "lds_bytes"} — "use": the measured in-step gate keeps the folded kernel for this shape."""
+    import ctypes
+    out = [ctypes.c_int() for _ in range(5)]
+    rc = _l.load().aldm_xattn_fold_plan(B, L, C, heads, Lk, *[ctypes.byref(o) for o in out])
+    plan = {k: o.value for k, o in zip(("tile_rows", "col_splits", "waves", "blocks", "lds_bytes"), out)}
+    plan["supported"] = rc >= 1
+    plan["use"] = rc == 2
+    return plan
+
+
+def xattn_fold_applies(B: int, L: int, C: int, heads: int, Lk: int) -> bool:
+    """Whether BasicTransformerBlock.run takes the folded kernel for this cross-attention: DMA mode, a bf16 / fp16 product mode
+    (f32 keeps the unfolded path), C % 32 == 0, at most 8 keys, L % 32 == 0, the switch on for this width, and the planner's gate."""
+    if not use_dma() or MMA_MODE == "f32" or XATTN_FOLD is False:
+        return False
+    if C % 32 != 0 or Lk > XATTN_FOLD_MAX_KEYS or Lk < 1 or L % 32 != 0 or heads * 32 != C:
+        return False
+    if XATTN_FOLD is not True and C not in XATTN_FOLD:
+        return False
+    return xattn_fold_plan(B, L, C, heads, Lk)["use"]
+
+
+class XattnFold:
+    """The folded operands of one cross-attention site for one context: Mq / Mo as the 3-part bf16 images xattn_folded reads
+    (include/aldm_hip.h).  The buffers are allocated once; prepare() rewrites them in place, so a captured step graph that reads
+    them sees the next job's context after a refresh.  2 * 6 * B * C * roundup(C / 4, 32) bytes."""
+
+    def __init__(self, B: int, C: int, heads: int, Lk: int, device):
+        n = _l.load().aldm_xattn_fold_bytes(B, C)
+        self.B, self.C, self.heads, self.Lk = B, C, heads, Lk
+        self.mq = torch.empty(n, device=device, dtype=torch.uint8)
+        self.mo = torch.empty(n, device=device, dtype=torch.uint8)
+
+    def prepare(self, kv: torch.Tensor, wq: torch.Tensor, wout: torch.Tensor) -> "XattnFold":
+        """kv: the cached K | V projection [B, Lk, 2C]; wq / wout: to_q.weight / to_out[0].weight [C, C], fp32 on the device."""
+        _chk(kv, "xattn_fold.kv")
+        _chk(wq, "xattn_fold.wq")
+        _chk(wout, "xattn_fold.wout")
+        assert tuple(kv.shape) == (self.B, self.Lk, 2 * self.C), (tuple(kv.shape), self.B, self.Lk, self.C)
+        assert tuple(wq.shape) == (self.C, self.C) and tuple(wout.shape) == (self.C, self.C)
+        _l.check(_l.load().aldm_xattn_fold_prepare(kv.data_ptr(), wq.data_ptr(), wout.data_ptr(), self.mq.data_ptr(),
+                                                   self.mo.data_ptr(), self.B, self.C, self.heads, self.Lk, _stream()),
+                 "xattn_fold_prepare")
+        return self
+
+
+def xattn_folded(h: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, fold: XattnFold, b_out: torch.Tensor,
+                 mask: Optional[torch.Tensor] = None, eps: float = 1e-5, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """h + to_out(attention(to_q(LayerNorm(h)), K, V, mask)) for a context of at most 8 keys, in one launch over the folded
+    operands (aldm_xattn_folded).  h: [B, L, C]; mask: [B, Lk] (1 = keep) or None; out (optional) must not alias h."""
+    _chk(h, "xattn_folded.h")
+    B, L, C = h.shape
+    assert (B, C) == (fold.B, fold.C), ((B, C), (fold.B, fold.C))
+    if out is None:
+        out = torch.empty_like(h)
+    else:
+        _chk(out, "xattn_folded.out")
+        assert out.shape == h.shape and out.data_ptr() != h.data_ptr()
+    if mask is not None:
+        mask = mask.to(torch.float32).reshape(B, fold.Lk).contiguous()
+    _l.check(_l.load().aldm_xattn_folded(h.data_ptr(), out.data_ptr(), gamma.data_ptr(), beta.data_ptr(), eps, fold.mq.data_ptr(),
+                                         fold.mo.data_ptr(), b_out.data_ptr(), _p(mask), B, L, C, fold.heads, fold.Lk, _stream()),
+             "xattn_folded")
+    return out
+
+
 def rmsnorm(x: torch.Tensor, weight: torch.Tensor, eps: float = 1e-6) -> torch.Tensor:
     """T5LayerNorm over the last dim: weight * x * rsqrt(mean(x^2) + eps)."""
     _chk(x, "rmsnorm.x")

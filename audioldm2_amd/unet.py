@@ -181,21 +181,35 @@ class BasicTransformerBlock(nn.Module):
         self.heads = n_heads
         self.dim = dim
         self._pk = None
-        self._kv = None  # [(context tensor, its _version, K|V projection)], newest first — see _context_kv
+        self._kv = None  # [(context tensor, its _version, K|V projection, folded operands or None)], newest first — see _context_kv
 
-    def _context_kv(self, context, pk):
+    def _fold_applies(self, h, context):
+        """Whether this cross-attention runs as the folded kernel (ops.xattn_folded): a context of at most 8 keys — the AudioMAE
+        context; FLAN-T5's 32 and more keys give heads * Lk >= C, where folding saves nothing — one context row per sample, and
+        everything ops.xattn_fold_applies asks of the mode, the shape and the planner's measured gate."""
+        return (context.dim() == 3 and context.shape[0] == h.shape[0]
+                and ops.xattn_fold_applies(h.shape[0], h.shape[1], self.dim, self.heads, context.shape[1]))
+
+    def _context_kv(self, context, pk, want_fold=False):
         """K/V projection of the cross-attention context (attention.py:336-337).  The context is the
         same tensor for all 200 DDIM steps, so the projection is computed once and reused while the
         SAME tensor object (unmodified: same _version) is passed again.  The cache holds a reference to
-        the context, so its storage cannot be recycled under us."""
+        the context, so its storage cannot be recycled under us.
+        want_fold: also the folded operands Mq / Mo built from the fresh projection (ops.XattnFold), kept in the same cache entry
+        (context, version, kv, fold) and dropped with it.  They cost 6 * B * C * roundup(C / 4, 32) bytes each: 169 MB per job on
+        the headline model (batch 16: 5 x 3.1 + 5 x 7.1 + 6 x 19.7 MB).  Returns (kv, fold or None)."""
         for c in (self._kv or ()):
-            if c[0] is context and c[1] == context._version:
-                return c[2]
+            if c[0] is context and c[1] == context._version and (c[3] is not None or not want_fold):
+                return c[2], c[3]
         kv = ops.linear(context, pk["kv2"])
+        fold = None
+        if want_fold:
+            fold = ops.XattnFold(context.shape[0], self.dim, self.heads, context.shape[1], kv.device)
+            fold.prepare(kv, pk["wq2"], pk["wout2"])
         if not torch.cuda.is_current_stream_capturing():  # graph-pool memory must not outlive the graph
             # two entries: the uncond and the cond context when CFG runs as two concurrent half passes
-            self._kv = [(context, context._version, kv)] + list(self._kv or ())[:1]
-        return kv
+            self._kv = [(context, context._version, kv, fold)] + list(self._kv or ())[:1]
+        return kv, fold
 
     def _prepare(self):
         if self._pk is None:
@@ -211,10 +225,31 @@ class BasicTransformerBlock(nn.Module):
                 q2=ops.pack_conv(a2.to_q.weight),
                 kv2=ops.pack_conv(torch.cat([a2.to_k.weight, a2.to_v.weight], 0)),
                 out2=ops.pack_conv(a2.to_out[0].weight, a2.to_out[0].bias),
+                # plain fp32 copies: the operands of the once-per-job fold (ops.XattnFold.prepare) and the folded kernel's bias
+                wq2=f(a2.to_q.weight), wout2=f(a2.to_out[0].weight), bout2=f(a2.to_out[0].bias),
                 ff1=ops.pack_geglu(self.ff.net[0].proj.weight, self.ff.net[0].proj.bias),
                 ff2=ops.pack_conv(self.ff.net[2].weight, self.ff.net[2].bias),
             )
         return self._pk
+
+    def _attn2_unfolded(self, h, context, mask, pk, so, pre):
+        """h + to_out(attn2(norm2(h), context)) launch by launch (attention.py:408)."""
+        C = self.dim
+        n = ops.layernorm(h, *pk["ln"][1], split_out=so)
+        if context is None:
+            if pk["qkv2"] is None:
+                raise RuntimeError("attn2 was built with a context_dim but no context was provided")
+            if pre and pk["qkv2"].bias is None:
+                q, kimg, vtimg = ops.linear_qkv(n, pk["qkv2"], self.heads, h.shape[1])
+                a = ops.attention_presplit(q, kimg, vtimg, self.heads, split_out=so)
+            else:
+                qkv = ops.linear(n, pk["qkv2"])
+                a = ops.attention(qkv[:, :, :C], qkv[:, :, C:2 * C], qkv[:, :, 2 * C:], self.heads, split_out=so)
+        else:
+            q = ops.linear(n, pk["q2"])
+            kv, _ = self._context_kv(context, pk)
+            a = ops.attention(q, kv[:, :, :C], kv[:, :, C:], self.heads, mask=mask, split_out=so)
+        return ops.linear(a, pk["out2"], res=h)
 
     def run(self, h, context=None, mask=None, want_split=False):
         """h: [B, L, C] tokens.  attention.py:406-410 (mask is ignored when context is None: :400-404).
@@ -236,21 +271,12 @@ class BasicTransformerBlock(nn.Module):
             qkv = ops.linear(n, pk["qkv1"])
             a = ops.attention(qkv[:, :, :C], qkv[:, :, C:2 * C], qkv[:, :, 2 * C:], self.heads, split_out=so)
         h = ops.linear(a, pk["out1"], res=h)
-        n = ops.layernorm(h, *pk["ln"][1], split_out=so)
-        if context is None:
-            if pk["qkv2"] is None:
-                raise RuntimeError("attn2 was built with a context_dim but no context was provided")
-            if pre and pk["qkv2"].bias is None:
-                q, kimg, vtimg = ops.linear_qkv(n, pk["qkv2"], self.heads, h.shape[1])
-                a = ops.attention_presplit(q, kimg, vtimg, self.heads, split_out=so)
-            else:
-                qkv = ops.linear(n, pk["qkv2"])
-                a = ops.attention(qkv[:, :, :C], qkv[:, :, C:2 * C], qkv[:, :, 2 * C:], self.heads, split_out=so)
+        if context is not None and self._fold_applies(h, context):
+            # short fixed context: norm2 + to_q + attention + to_out + residual in one launch over the folded operands
+            _, fold = self._context_kv(context, pk, want_fold=True)
+            h = ops.xattn_folded(h, *pk["ln"][1], fold, pk["bout2"], mask=mask)
         else:
-            q = ops.linear(n, pk["q2"])
-            kv = self._context_kv(context, pk)
-            a = ops.attention(q, kv[:, :, :C], kv[:, :, C:], self.heads, mask=mask, split_out=so)
-        h = ops.linear(a, pk["out2"], res=h)
+            h = self._attn2_unfolded(h, context, mask, pk, so, pre)
         n = ops.layernorm(h, *pk["ln"][2], split_out=so)
         g = ops.linear_geglu(n, pk["ff1"], split_out=so)  # Linear(C, 8C) + x*gelu(gate) in one GEMM (attention.py:37-45)
         if want_split and so:
@@ -458,26 +484,29 @@ class UNetModel(nn.Module):
                 m._kv = None
 
     def collect_context_kv(self, contexts):
-        """[(block, context, kv)] for every cached cross-attention K/V projection of the given context tensors.  A
-        captured step graph reads exactly these kv buffers: the graph-cache entry keeps this list (and with it the
-        buffers) alive, so nothing a later run does to the blocks' 2-entry lookup lists can free or recycle them."""
+        """[(block, context, kv, fold)] for every cached cross-attention K/V projection of the given context tensors (fold: the
+        folded operands built from it, or None).  A captured step graph reads exactly these buffers: the graph-cache entry keeps
+        this list (and with it the buffers) alive, so nothing a later run does to the blocks' 2-entry lookup lists can free or
+        recycle them."""
         out = []
         for m in self.modules():
             if isinstance(m, BasicTransformerBlock) and m._kv:
-                for ctx, _ver, kv in m._kv:
+                for ctx, _ver, kv, fold in m._kv:
                     if any(ctx is c for c in contexts):
-                        out.append((m, ctx, kv))
+                        out.append((m, ctx, kv, fold))
         return out
 
     def refresh_context_kv(self, entries):
         """Recompute IN PLACE the K/V projections a captured step graph reads (`entries` from collect_context_kv; the
-        contexts' contents were overwritten for a new sampling run) and put them back at the front of each block's
-        lookup list.  Returns the number of projections refreshed."""
+        contexts' contents were overwritten for a new sampling run), then the folded operands built from them, also in place,
+        and put them back at the front of each block's lookup list.  Returns the number of projections refreshed."""
         n = 0
-        for m, ctx, kv in entries:
+        for m, ctx, kv, fold in entries:
             pk = m._prepare()
             ops.linear(ctx, pk["kv2"], out=kv)
-            m._kv = [(ctx, ctx._version, kv)] + [c for c in (m._kv or ()) if c[2] is not kv][:1]
+            if fold is not None:
+                fold.prepare(kv, pk["wq2"], pk["wout2"])
+            m._kv = [(ctx, ctx._version, kv, fold)] + [c for c in (m._kv or ()) if c[2] is not kv][:1]
             n += 1
         return n
 

@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 /* ---- library / error ------------------------------------------------------------------ */
-int aldm_version(void);              /* ABI version (20), bumped on any struct / entry change */
+int aldm_version(void);              /* ABI version (21), bumped on any struct / entry change */
 const char* aldm_last_error(void);   /* message of the last failing call on this thread     */
 
 /* ---- activations usable as prologue (applied to the gathered input) or epilogue -------- */
@@ -402,6 +402,38 @@ int aldm_attention_query_tiles(int B, int heads, int Lq);
 int aldm_attention_d32_presplit_f16(const float* q, const void* k_split, const void* vt_split, float* out, void* out_split,
                                     int out_parts, float out_scale, int B, int heads, int Lq, int Lk, int ldq, int ldo,
                                     float scale, float q_scale, float k_scale, float v_scale, void* stream);
+/* ---- folded cross-attention on a short context (ABI v21) ----------------------------------------------------------------
+ * The context of a cross-attention sublayer is fixed for a whole sampling run, so with Lk <= 8 keys the two C x C projections
+ * around the attention fold into two per-sample operands, once per job (N = heads * 8 score columns, column n = head * 8 + key,
+ * Np = N rounded up to 32; key columns >= Lk and the columns >= N are zero):
+ *   Mq_b[c, n] = 32^-1/2 log2(e) sum_d Wq[head*32 + d, c] k_b[key, head*32 + d]        (C x Np; scores come out in log2 units)
+ *   Mo_b[n, c] = sum_d v_b[key, head*32 + d] Wout[c, head*32 + d]                      (Np x C)
+ *   out = softmax_per_head(LayerNorm(h) Mq_b, mask) Mo_b + b_out + h
+ * aldm_xattn_fold_prepare writes both as 3-part bf16 images (every entry a 32-term dot product accumulated in fp64, rounded ONCE
+ * to fp32, then split exactly: x = hi + mid + lo), in the order the kernel's matrix instructions take them — one 16-byte piece =
+ * one lane's operand fragment (lane l: r = l & 31, u = l >> 5; element j = 0..7), 1 KiB per (tile, k-step, part):
+ *   mq_img: [b][n tile = Np/32][k step = C/16][part 0..2][lane 64][8] bf16, element = Mq_b[16 kstep + 8 u + j, 32 ntile + r]
+ *   mo_img: [b][c tile = C/32][n step = Np/16][part 0..2][lane 64][8] bf16, element = Mo_b[16 nstep + 8 u + j, 32 ctile + r]
+ * aldm_xattn_fold_bytes = the size of either image (they are equally large).  kv: the cached projection [B, Lk, 2C] (k | v);
+ * wq / wout: to_q.weight / to_out[0].weight, [C, C] row-major fp32.  The images are the caller's: a second prepare into the
+ * same buffers refreshes them in place.
+ * aldm_xattn_folded is the sublayer in one launch: h, out [B*L, C] fp32 (out must not alias h), mask [B, Lk] (a key takes part
+ * iff its entry == 1; masked keys score -FLT_MAX like aldm_attention_d32, so a row with every key masked is uniform over the
+ * Lk real keys) or NULL.  Needs C % 32 == 0, heads * 32 == C, 1 <= Lk <= 8, L % 32 == 0, and C <= 640: a block keeps its
+ * rows and probabilities as 3-part images in the 160 KiB LDS.
+ * aldm_xattn_fold_plan (host only, like aldm_groupnorm_plan): the launch geometry of a shape — tile_rows (32 | 64 rows of ONE
+ * sample per block), col_splits (blocks that share a row tile, each recomputing the scores and writing C / col_splits output
+ * columns), waves per block, blocks, lds_bytes.  Returns 0 when the kernel does not support the shape, 1 when it does but the
+ * measured in-step gate (docs/experiments_r1-r6.md §10.8) keeps the unfolded path for it, 2 when the step should use it.  Out
+ * pointers may be NULL.                                                                                                      */
+int aldm_xattn_fold_plan(int B, int L, int C, int heads, int Lk, int* tile_rows, int* col_splits, int* waves, int* blocks,
+                         int* lds_bytes);
+int64_t aldm_xattn_fold_bytes(int B, int C);
+int aldm_xattn_fold_prepare(const float* kv, const float* wq, const float* wout, void* mq_img, void* mo_img, int B, int C,
+                            int heads, int Lk, void* stream);
+int aldm_xattn_folded(const float* h, float* out, const float* gamma, const float* beta, float eps, const void* mq_img,
+                      const void* mo_img, const float* b_out, const float* mask, int B, int L, int C, int heads, int Lk,
+                      void* stream);
 /* Windowed relative-position self-attention of the VITS phoneme encoder (phoneme_encoder/attentions.py:239-289,
  * window_size = `window` <= 8, shared heads): per head h (channels [h*d, (h+1)*d), d <= 128)
  *   s[i, j] = (q_i/sqrt(d)).k_j + [|j-i| <= window] (q_i/sqrt(d)).emb_k[j-i+window];  s = -1e4 where mask_i*mask_j == 0;

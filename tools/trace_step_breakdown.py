@@ -46,6 +46,8 @@ def category(n):
         return "GEMM: split-K reduce"
     if n.startswith("igemm"):
         return "GEMM: register-staged"
+    if n.startswith("xattn_fold"):
+        return "folded cross-attention (LN + scores + softmax + out)"
     if n.startswith("attention"):
         return "attention"
     if n.startswith("gn_"):
