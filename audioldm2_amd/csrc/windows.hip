@@ -1,6 +1,7 @@
 // windows.hip — the per-step launches of windowed (long-form) diffusion: the window gather in front of the UNet pass and the
 // tapered, normalised overlap-add behind it, and the gather fused with the inpainting blend of a kept source on
-// the long latent (§9f), and the wrap-around forms of the three for ring plans (§9g).  All are HBM-bound copies with at most `cover` multiply-adds (the blend: five operations) per
+// the long latent (§9f), the wrap-around forms of the three for ring plans (§9g), and their forms over the rows of a prompt timeline
+// (one row per window and prompt, the merge weighted per row and frame; §9h).  All are HBM-bound copies with at most `cover` multiply-adds (the blend: five operations) per
 // element: 16-byte accesses along the contiguous F axis where F % 4 == 0 and the pointers are aligned, a scalar path otherwise,
 // grid-stride, 64-bit indexing, fp32.  The window starts travel as a kernel argument (aldm_window_starts, by value): a captured
 // step graph carries them, there is no device table and no copy inside a capture; every index into them is wave-uniform.
@@ -253,6 +254,121 @@ static inline bool spans_overlap(const float* a, int64_t na, const float* b, int
     return (uintptr_t)a < (uintptr_t)(b + nb) && (uintptr_t)b < (uintptr_t)(a + na);
 }
 
+// ---- prompt timelines: a ROW is one window under one prompt, so rows may share a start ------------------------------
+// Siblings again: the linear and ring kernels above stay what they were.  The row starts travel by value (aldm_window_rows, 64
+// entries, 260 bytes of kernel arguments); every index into them is wave-uniform.
+
+// win[(r*B + b), c, p, f] = x[b, c, s_r + p, f].  blockIdx.y = r: window_gather_kernel over rows (rows of one window are equal
+// copies; each is read from x again — the long latent is R/W-th of the traffic and stays in L2).
+template <int V>
+__global__ void window_gather_rows_kernel(const float* __restrict__ x, float* __restrict__ win, aldm_window_rows st, int T, int F,
+                                          int64_t per_row, int64_t total) {
+    typedef typename vec_of<V>::type vec;
+    const int r = blockIdx.y;
+    const int64_t src0 = (int64_t)st.s[r] * F;
+    const int64_t plane = (int64_t)T * F;
+    float* dst = win + (int64_t)r * total * V;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t bc = i / per_row, off = i - bc * per_row;
+        *reinterpret_cast<vec*>(dst + i * V) = *reinterpret_cast<const vec*>(x + bc * plane + src0 + off * V);
+    }
+}
+
+// out[h, b, c, t, f] = sum over the rows r that cover t with wr[r, t - s_r] != 0, ascending r, of wr[r, t - s_r] * win[h, r*B + b, c,
+// t - s_r, f]: the first kept term a plain multiply, every later one a fused multiply-add.  A row whose weight at the frame is exactly
+// 0 is skipped BEFORE its win element is loaded: a prompt that is silent there contributes nothing (no 0 * NaN) and costs no
+// traffic.  The weight depends on (r, t) only: the skip is uniform over the F lanes of an output row.  Gather form, no atomics.
+template <int V>
+__global__ void window_merge_rows_kernel(const float* __restrict__ win, const float* __restrict__ wr, float* __restrict__ out,
+                                         aldm_window_rows st, int B, int C, int T, int Tw, int F, int64_t total) {
+    typedef typename vec_of<V>::type vec;
+    const int FV = F / V;
+    const int R = st.n;
+    const int64_t wplane = (int64_t)Tw * F;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        int64_t q = i / FV;
+        const int fv = (int)(i - q * FV);
+        const int t = (int)(q % T);
+        q /= T;
+        const int c = (int)(q % C);
+        q /= C;
+        const int b = (int)(q % B);
+        const int64_t h = q / B;
+        vec acc = vec(0.0f);
+        bool first = true;
+        for (int r = 0; r < R; ++r) {
+            const int p = t - st.s[r];
+            if (p < 0 || p >= Tw) continue;
+            const float wv = wr[(int64_t)r * Tw + p];
+            if (wv == 0.0f) continue;
+            const vec e = *reinterpret_cast<const vec*>(win + ((((h * R + r) * B + b) * C + c) * wplane + (int64_t)p * F + fv * V));
+            if (first) {
+                acc = wv * e;
+                first = false;
+            } else if constexpr (V == 4) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) acc[k] = __builtin_fmaf(wv, e[k], acc[k]);
+            } else {
+                acc = __builtin_fmaf(wv, e, acc);
+            }
+        }
+        *reinterpret_cast<vec*>(out + i * V) = acc;
+    }
+}
+
+// window_blend_gather_kernel over rows: the same blend expression, operation order and row selection of the tables, then a copy
+// into every covering row.  A row position maps to one frame, so every element of win has exactly one writer, and the row starts
+// tile [0, T), so every element is written.
+template <int V>
+__global__ void window_blend_gather_rows_kernel(float* __restrict__ x, const float* __restrict__ x0, const float* __restrict__ qnoise,
+                                                const float* __restrict__ mask, const float* __restrict__ blend_coef,
+                                                const int* __restrict__ step_idx, int q_rows, int coef_rows,
+                                                float* __restrict__ win, aldm_window_rows st, int B, int C, int T, int Tw, int F,
+                                                int64_t total) {
+    typedef typename vec_of<V>::type vec;
+    int s = step_idx ? *step_idx : 0;
+    s = s < 0 ? 0 : s;
+    const int qr = s < q_rows ? s : q_rows - 1, cr = s < coef_rows ? s : coef_rows - 1;
+    const float sa = blend_coef[2 * cr], so = blend_coef[2 * cr + 1];
+    const float* qn = qnoise + (int64_t)qr * total * V;
+    const int FV = F / V;
+    const int R = st.n;
+    const int64_t wplane = (int64_t)Tw * F;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        int64_t q = i / FV;
+        const int fv = (int)(i - q * FV);
+        const int t = (int)(q % T);
+        q /= T;
+        const int c = (int)(q % C);
+        const int64_t b = q / C;
+        const vec m = *reinterpret_cast<const vec*>(mask + i * V);
+        const vec orig = sa * *reinterpret_cast<const vec*>(x0 + i * V) + so * *reinterpret_cast<const vec*>(qn + i * V);
+        const vec v = orig * m + (1.0f - m) * *reinterpret_cast<const vec*>(x + i * V);
+        *reinterpret_cast<vec*>(x + i * V) = v;
+        for (int r = 0; r < R; ++r) {
+            const int p = t - st.s[r];
+            if (p < 0 || p >= Tw) continue;
+            *reinterpret_cast<vec*>(win + (((int64_t)r * B + b) * C + c) * wplane + (int64_t)p * F + fv * V) = v;
+        }
+    }
+}
+
+// the host-side checks the row entries share: the shape, and row starts (non-decreasing: a window under several prompts repeats its
+// start) whose windows of Tw tile [0, T)
+static int window_rows_args_ok(const char* name, const aldm_window_rows& st, int B, int C, int T, int Tw, int F) {
+    ALDM_CHECK(B > 0 && C > 0 && F > 0 && Tw > 0 && T >= Tw, "%s: bad shape (B=%d, C=%d, T=%d, Tw=%d, F=%d)", name, B, C, T, Tw, F);
+    ALDM_CHECK(st.n >= 1 && st.n <= ALDM_MAX_ROWS, "%s: %d rows (1 <= n <= %d)", name, st.n, ALDM_MAX_ROWS);
+    ALDM_CHECK(st.s[0] == 0, "%s: rows[0]=%d must be 0", name, st.s[0]);
+    for (int r = 1; r < st.n; ++r) {
+        ALDM_CHECK(st.s[r] >= st.s[r - 1], "%s: row starts must not decrease (rows[%d]=%d after %d)", name, r, st.s[r], st.s[r - 1]);
+        ALDM_CHECK(st.s[r] - st.s[r - 1] <= Tw, "%s: gap of %d frames between rows[%d] and rows[%d] exceeds Tw=%d: frames without "
+                   "a row", name, st.s[r] - st.s[r - 1], r - 1, r, Tw);
+    }
+    ALDM_CHECK(st.s[st.n - 1] == T - Tw, "%s: the last row start %d must be T - Tw = %d", name, st.s[st.n - 1], T - Tw);
+    ALDM_CHECK((int64_t)st.n * B * C * Tw * F <= (1ll << 40), "%s: %lld row elements", name, (long long)st.n * B * C * Tw * F);
+    return 0;
+}
+
 }  // namespace aldm
 
 using namespace aldm;
@@ -386,5 +502,72 @@ extern "C" int aldm_window_merge_ring(const float* win, const float* wn, float* 
                            B, W, C, T, Tw, F, n_out);
     }
     ALDM_LAUNCH_CHECK("aldm_window_merge_ring");
+    return 0;
+}
+
+// ---- the row entries (ABI v22, prompt timelines): rows = (window, prompt) pairs, starts non-decreasing --------------------------------
+extern "C" int aldm_window_gather_rows(const float* x, float* win, aldm_window_rows rows, int B, int C, int T, int Tw, int F,
+                                       void* stream) {
+    ALDM_CHECK(x && win, "aldm_window_gather_rows: null pointer");
+    if (window_rows_args_ok("aldm_window_gather_rows", rows, B, C, T, Tw, F) != 0) return -1;
+    const int64_t n_x = (int64_t)B * C * T * F, n_w = (int64_t)rows.n * B * C * Tw * F;
+    ALDM_CHECK(!spans_overlap(x, n_x, win, n_w), "aldm_window_gather_rows: win overlaps x");
+    const int64_t per_window = (int64_t)B * C * Tw * F;
+    const dim3 block(256);
+    if (F % 4 == 0 && (((uintptr_t)x | (uintptr_t)win) & 15) == 0) {
+        const dim3 grid(win_blocks(per_window / 4), rows.n);
+        hipLaunchKernelGGL(window_gather_rows_kernel<4>, grid, block, 0, (hipStream_t)stream, x, win, rows, T, F,
+                           (int64_t)Tw * F / 4, per_window / 4);
+    } else {
+        const dim3 grid(win_blocks(per_window), rows.n);
+        hipLaunchKernelGGL(window_gather_rows_kernel<1>, grid, block, 0, (hipStream_t)stream, x, win, rows, T, F, (int64_t)Tw * F,
+                           per_window);
+    }
+    ALDM_LAUNCH_CHECK("aldm_window_gather_rows");
+    return 0;
+}
+
+extern "C" int aldm_window_blend_gather_rows(float* x, const float* x0, const float* qnoise, const float* mask,
+                                             const float* blend_coef, const int* step_idx, int q_rows, int coef_rows, float* win,
+                                             aldm_window_rows rows, int B, int C, int T, int Tw, int F, void* stream) {
+    ALDM_CHECK(x && x0 && qnoise && mask && blend_coef && win, "aldm_window_blend_gather_rows: null pointer");
+    if (window_rows_args_ok("aldm_window_blend_gather_rows", rows, B, C, T, Tw, F) != 0) return -1;
+    ALDM_CHECK(q_rows >= 1 && coef_rows >= 1, "aldm_window_blend_gather_rows: q_rows=%d and coef_rows=%d must be >= 1", q_rows,
+               coef_rows);
+    const int64_t n_x = (int64_t)B * C * T * F, n_w = (int64_t)rows.n * B * C * Tw * F, n_q = (int64_t)q_rows * n_x;
+    ALDM_CHECK(!spans_overlap(win, n_w, x, n_x) && !spans_overlap(win, n_w, x0, n_x) && !spans_overlap(win, n_w, qnoise, n_q) &&
+               !spans_overlap(win, n_w, mask, n_x), "aldm_window_blend_gather_rows: win overlaps x, x0, qnoise or mask");
+    ALDM_CHECK(!spans_overlap(x, n_x, x0, n_x) && !spans_overlap(x, n_x, qnoise, n_q) && !spans_overlap(x, n_x, mask, n_x),
+               "aldm_window_blend_gather_rows: x overlaps x0, qnoise or mask");
+    const dim3 block(256);
+    if (F % 4 == 0 &&
+        (((uintptr_t)x | (uintptr_t)x0 | (uintptr_t)qnoise | (uintptr_t)mask | (uintptr_t)win) & 15) == 0) {
+        hipLaunchKernelGGL(window_blend_gather_rows_kernel<4>, dim3(win_blocks(n_x / 4)), block, 0, (hipStream_t)stream, x, x0,
+                           qnoise, mask, blend_coef, step_idx, q_rows, coef_rows, win, rows, B, C, T, Tw, F, n_x / 4);
+    } else {
+        hipLaunchKernelGGL(window_blend_gather_rows_kernel<1>, dim3(win_blocks(n_x)), block, 0, (hipStream_t)stream, x, x0, qnoise,
+                           mask, blend_coef, step_idx, q_rows, coef_rows, win, rows, B, C, T, Tw, F, n_x);
+    }
+    ALDM_LAUNCH_CHECK("aldm_window_blend_gather_rows");
+    return 0;
+}
+
+extern "C" int aldm_window_merge_rows(const float* win, const float* wr, float* out, aldm_window_rows rows, int H, int B, int C, int T,
+                                      int Tw, int F, void* stream) {
+    ALDM_CHECK(win && wr && out, "aldm_window_merge_rows: null pointer");
+    ALDM_CHECK(H == 1 || H == 2, "aldm_window_merge_rows: H=%d: 1, or 2 for the [uncond ; cond] pair", H);
+    if (window_rows_args_ok("aldm_window_merge_rows", rows, B, C, T, Tw, F) != 0) return -1;
+    const int64_t n_out = (int64_t)H * B * C * T * F, n_w = (int64_t)H * rows.n * B * C * Tw * F;
+    ALDM_CHECK(!spans_overlap(out, n_out, win, n_w) && !spans_overlap(out, n_out, wr, (int64_t)rows.n * Tw),
+               "aldm_window_merge_rows: out overlaps win or wr");
+    const dim3 block(256);
+    if (F % 4 == 0 && (((uintptr_t)win | (uintptr_t)out) & 15) == 0) {
+        hipLaunchKernelGGL(window_merge_rows_kernel<4>, dim3(win_blocks(n_out / 4)), block, 0, (hipStream_t)stream, win, wr, out, rows,
+                           B, C, T, Tw, F, n_out / 4);
+    } else {
+        hipLaunchKernelGGL(window_merge_rows_kernel<1>, dim3(win_blocks(n_out)), block, 0, (hipStream_t)stream, win, wr, out, rows, B,
+                           C, T, Tw, F, n_out);
+    }
+    ALDM_LAUNCH_CHECK("aldm_window_merge_rows");
     return 0;
 }

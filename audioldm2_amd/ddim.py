@@ -186,6 +186,10 @@ class DDIMSampler(SamplerBase):
             ent["x_cur"].copy_(img)
             ent["coef_all"].copy_(plan.coef)
             ent["t_tab"].copy_(plan.t_tab)
+            if plan.win is not None and plan.win.wr is not None:
+                # a row plan: the captured merge node reads the entry's weight buffer; this job's timeline goes INTO it (the key
+                # holds the row geometry only), outside any capture
+                ent["win"].wr.copy_(plan.win.wr)
         else:
             # static buffers = the graph's inputs
             ent = {"x_cur": img.clone(), "pred_x0": torch.empty_like(img), "t_cur": plan.t_tab[0].clone(),

@@ -11,7 +11,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ALDM_LIB_PATH") or os.path.join(_HERE, "libaldm_hip.so")  # override: debug builds
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 ACT_NONE, ACT_SILU, ACT_LRELU, ACT_TANH, ACT_LOGCLAMP, ACT_GELU, ACT_GELU_TANH = range(7)
 B_PACKED, B_NT = 0, 1
@@ -63,6 +63,15 @@ class WindowStarts(C.Structure):
     """Mirror of `struct aldm_window_starts` (include/aldm_hip.h), passed by value: the window starts of a long-form plan."""
 
     _fields_ = [("n", C.c_int), ("s", C.c_int * MAX_WINDOWS)]
+
+
+MAX_ROWS = 64
+
+
+class WindowRows(C.Structure):
+    """Mirror of `struct aldm_window_rows` (include/aldm_hip.h), passed by value: the row starts of a prompt timeline's row plan."""
+
+    _fields_ = [("n", C.c_int), ("s", C.c_int * MAX_ROWS)]
 
 
 _SIGS = {
@@ -198,6 +207,13 @@ _SIGS = {
     "aldm_window_blend_gather_ring": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                                 C.c_int, C.c_void_p, WindowStarts, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                 C.c_int, C.c_void_p]),
+    "aldm_window_gather_rows": (C.c_int, [C.c_void_p, C.c_void_p, WindowRows, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.c_void_p]),
+    "aldm_window_merge_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, WindowRows, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_int, C.c_void_p]),
+    "aldm_window_blend_gather_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                C.c_int, C.c_void_p, WindowRows, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                C.c_void_p]),
     "aldm_axpby": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int64,
                              C.c_void_p]),
     "aldm_reflect_pad_1d": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,

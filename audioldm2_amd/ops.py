@@ -1710,6 +1710,29 @@ def _window_starts(plan) -> "_l.WindowStarts":
     return st
 
 
+def _window_rows(plan) -> "_l.WindowRows":
+    """A row plan's row starts (windows.row_plan) as the by-value kernel argument (built once per plan)."""
+    st = getattr(plan, "_rows_arg", None)
+    if st is None:
+        if len(plan.row_starts) > _l.MAX_ROWS:
+            raise RuntimeError(f"row plan: {len(plan.row_starts)} rows, at most {_l.MAX_ROWS}")
+        st = _l.WindowRows()
+        st.n = len(plan.row_starts)
+        for r, s in enumerate(plan.row_starts):
+            st.s[r] = int(s)
+        plan._rows_arg = st
+    return st
+
+
+def _has_rows(plan) -> bool:
+    return getattr(plan, "rows", None) is not None
+
+
+def _window_groups(plan) -> int:
+    """How many row groups of B samples the window tensors of `plan` hold: its rows (a row plan), else its windows."""
+    return plan.R if _has_rows(plan) else plan.W
+
+
 def _window_entry(plan, name: str):
     """The C entry of a window launch: `name`, or its wrap-around form `name`_ring for a ring plan (windows.window_plan(...,
     ring=True); the argument lists are the same)."""
@@ -1727,18 +1750,23 @@ def _no_overlap(out: torch.Tensor, what: str, others) -> None:
 def window_gather(x: torch.Tensor, plan, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The windows of a long tensor (aldm_window_gather): x [B, C, T, F] -> [W*B, C, Tw, F], row j*B + b = x[b, :, s_j:s_j + Tw]
     (window-major), a bit-exact copy.  `plan`: windows.window_plan(T, Tw, hop); `out`: write into this (it may not overlap x).  A
-    ring plan (plan.ring) takes aldm_window_gather_ring: row j*B + b = the frames (s_j + p) mod T, p in [0, Tw)."""
+    ring plan (plan.ring) takes aldm_window_gather_ring: row j*B + b = the frames (s_j + p) mod T, p in [0, Tw).  A row plan
+    (windows.row_plan) takes aldm_window_gather_rows: [R*B, C, Tw, F], row r*B + b = x[b, :, s_r:s_r + Tw] with the row starts s_r."""
     _chk(x, "window_gather.x")
     if x.dim() != 4 or x.shape[2] != plan.T or x.numel() == 0:
         raise RuntimeError(f"window_gather: x must be [B, C, T={plan.T}, F], got {tuple(x.shape)}")
     B, C, T, F = x.shape
-    shape = (plan.W * B, C, plan.Tw, F)
+    shape = (_window_groups(plan) * B, C, plan.Tw, F)
     if out is None:
         out = torch.empty(shape, device=x.device, dtype=torch.float32)
     _chk(out, "window_gather.out")
     if tuple(out.shape) != shape:
         raise RuntimeError(f"window_gather.out: expected {shape}, got {tuple(out.shape)}")
     _no_overlap(out, "window_gather.out", [(x, "x")])
+    if _has_rows(plan):
+        _l.check(_l.load().aldm_window_gather_rows(x.data_ptr(), out.data_ptr(), _window_rows(plan), B, C, T, plan.Tw, F, _stream()),
+                 "window_gather")
+        return out
     _l.check(_window_entry(plan, "aldm_window_gather")(x.data_ptr(), out.data_ptr(), _window_starts(plan), B, plan.W, C, T, plan.Tw, F,
                                           _stream()), "window_gather")
     return out
@@ -1751,7 +1779,8 @@ def window_blend_gather(x: torch.Tensor, x0: torch.Tensor, qnoise: torch.Tensor,
     window_gather.  x, x0, mask [B, C, T, F]; qnoise [q_rows, B, C, T, F], or [B, C, T, F] for one row; blend_coef [coef_rows, 2] =
     {sa, so}, or [2] for one row; step_idx (int32 [1] on the device, None: 0) selects row min(step_idx, rows - 1) of each table on
     the device.  `out`: write the windows into this.  out may overlap no operand, x none of x0, qnoise, mask.  A ring plan
-    (plan.ring) takes aldm_window_blend_gather_ring: the same blend, the window copies at their wrapped positions."""
+    (plan.ring) takes aldm_window_blend_gather_ring: the same blend, the window copies at their wrapped positions.  A row plan
+    (windows.row_plan) takes aldm_window_blend_gather_rows: the same blend, a copy into every covering row."""
     for t, n in ((x, "x"), (x0, "x0"), (qnoise, "qnoise"), (mask, "mask"), (blend_coef, "blend_coef")):
         _chk(t, "window_blend_gather." + n)
     if x.dim() != 4 or x.shape[2] != plan.T or x.numel() == 0:
@@ -1772,7 +1801,7 @@ def window_blend_gather(x: torch.Tensor, x0: torch.Tensor, qnoise: torch.Tensor,
     coef_rows = blend_coef.numel() // 2
     if step_idx is not None and (step_idx.dtype != torch.int32 or not step_idx.is_cuda or step_idx.numel() != 1):
         raise RuntimeError("window_blend_gather.step_idx: expected one int32 on the device")
-    shape = (plan.W * B, C, plan.Tw, F)
+    shape = (_window_groups(plan) * B, C, plan.Tw, F)
     if out is None:
         out = torch.empty(shape, device=x.device, dtype=torch.float32)
     _chk(out, "window_blend_gather.out")
@@ -1781,6 +1810,11 @@ def window_blend_gather(x: torch.Tensor, x0: torch.Tensor, qnoise: torch.Tensor,
     others = [(x0, "x0"), (qnoise, "qnoise"), (mask, "mask")]
     _no_overlap(out, "window_blend_gather.out", [(x, "x")] + others + [(blend_coef, "blend_coef")])
     _no_overlap(x, "window_blend_gather.x", others + [(blend_coef, "blend_coef")])
+    if _has_rows(plan):
+        _l.check(_l.load().aldm_window_blend_gather_rows(x.data_ptr(), x0.data_ptr(), qnoise.data_ptr(), mask.data_ptr(),
+                                                         blend_coef.data_ptr(), _p(step_idx), q_rows, coef_rows, out.data_ptr(),
+                                                         _window_rows(plan), B, C, T, plan.Tw, F, _stream()), "window_blend_gather")
+        return out
     _l.check(_window_entry(plan, "aldm_window_blend_gather")(x.data_ptr(), x0.data_ptr(), qnoise.data_ptr(), mask.data_ptr(),
                                                 blend_coef.data_ptr(), _p(step_idx), q_rows, coef_rows, out.data_ptr(),
                                                 _window_starts(plan), B, plan.W, C, T, plan.Tw, F, _stream()),
@@ -1788,28 +1822,44 @@ def window_blend_gather(x: torch.Tensor, x0: torch.Tensor, qnoise: torch.Tensor,
     return out
 
 
-def window_merge(win: torch.Tensor, plan, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+def window_merge(win: torch.Tensor, plan, out: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The tapered, normalised overlap-add of window-wise tensors (aldm_window_merge): win [W*B, C, Tw, F] -> [B, C, T, F], or
     win [2, W*B, C, Tw, F] (the [uncond ; cond] pair of a guided UNet pass) -> [2, B, C, T, F]; rows window-major as
     window_gather writes them.  Per output element the covering windows in ascending order, wn*e first, then one fmaf each, in
     fp32: bitwise reproducible.  `out`: write into this (it may not overlap win).  A ring plan (plan.ring) takes
-    aldm_window_merge_ring: the overlap-add round the circle of plan.T frames."""
+    aldm_window_merge_ring: the overlap-add round the circle of plan.T frames.  A row plan (windows.row_plan, prompt timelines)
+    takes aldm_window_merge_rows: win holds R*B rows, the weights are plan.wr [R, Tw], and a row whose weight at a frame is exactly 0
+    is skipped there, its element not even loaded.  `weights` (a row plan only): read the [R, Tw] weights from this device tensor
+    instead of the plan's own upload — the static buffer of a cached step graph, refilled per job."""
     from .windows import device_weights
     _chk(win, "window_merge.win")
+    W = _window_groups(plan)
     if win.dim() not in (4, 5) or (win.dim() == 5 and win.shape[0] != 2) or win.shape[-2] != plan.Tw or win.numel() == 0 \
-            or win.shape[-4] % plan.W != 0:
-        raise RuntimeError(f"window_merge: win must be [W*B, C, Tw, F] or [2, W*B, C, Tw, F] with W={plan.W}, Tw={plan.Tw}, got "
+            or win.shape[-4] % W != 0:
+        raise RuntimeError(f"window_merge: win must be [W*B, C, Tw, F] or [2, W*B, C, Tw, F] with W={W}, Tw={plan.Tw}, got "
                            f"{tuple(win.shape)}")
     H = 2 if win.dim() == 5 else 1
-    B, C, F = win.shape[-4] // plan.W, win.shape[-3], win.shape[-1]
+    B, C, F = win.shape[-4] // W, win.shape[-3], win.shape[-1]
     shape = ((2,) if win.dim() == 5 else ()) + (B, C, plan.T, F)
     if out is None:
         out = torch.empty(shape, device=win.device, dtype=torch.float32)
     _chk(out, "window_merge.out")
     if tuple(out.shape) != shape:
         raise RuntimeError(f"window_merge.out: expected {shape}, got {tuple(out.shape)}")
-    wn = device_weights(plan, win.device)
+    if weights is None:
+        wn = device_weights(plan, win.device)
+    else:
+        if not _has_rows(plan):
+            raise RuntimeError("window_merge.weights: only a row plan (windows.row_plan) reads its weights from a caller's buffer")
+        _chk(weights, "window_merge.weights")
+        if tuple(weights.shape) != (W, plan.Tw):
+            raise RuntimeError(f"window_merge.weights: expected {(W, plan.Tw)}, got {tuple(weights.shape)}")
+        wn = weights
     _no_overlap(out, "window_merge.out", [(win, "win"), (wn, "wn")])
+    if _has_rows(plan):
+        _l.check(_l.load().aldm_window_merge_rows(win.data_ptr(), wn.data_ptr(), out.data_ptr(), _window_rows(plan), H, B, C, plan.T,
+                                                  plan.Tw, F, _stream()), "window_merge")
+        return out
     _l.check(_window_entry(plan, "aldm_window_merge")(win.data_ptr(), wn.data_ptr(), out.data_ptr(), _window_starts(plan), H, B, plan.W, C,
                                          plan.T, plan.Tw, F, _stream()), "window_merge")
     return out

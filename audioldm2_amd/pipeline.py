@@ -277,6 +277,70 @@ class DiffusionWrapper(nn.Module):
 SAMPLERS = ("dpmpp_2m",)   # what `sampler=` names besides the reference's own choices (DDIM, use_plms=True, ancestral)
 
 
+def _timeline_batches(batch, boundaries, loop, who):
+    """The `batch` / `boundaries` arguments of a long-form job -> (the K batches of a prompt timeline, or None; the
+    batch whose mel, file names and negative prompt the job takes: the first).  Pure host; ValueError for a timeline that cannot
+    run: loop=True, no batch, batches of unequal size, a count of boundaries other than K-1, boundaries without a list of batches."""
+    if not isinstance(batch, (list, tuple)):
+        if boundaries is not None and len(list(boundaries)) > 0:
+            raise ValueError(f"{who}: boundaries= needs `batch` to be a list of batches, one per prompt of the timeline")
+        return None, batch
+    batches = list(batch)
+    if loop:
+        raise ValueError(f"{who}: a prompt timeline together with loop=True is not supported (a ring has no first prompt)")
+    if not batches:
+        raise ValueError(f"{who}: a prompt timeline needs at least one batch")
+    sizes = [len(b["text"]) for b in batches]
+    if len(set(sizes)) != 1:
+        raise ValueError(f"{who}: the batches of a prompt timeline must have one size, got {sizes}")
+    n = 0 if boundaries is None else len(list(boundaries))
+    if n != len(batches) - 1:
+        raise ValueError(f"{who}: {len(batches)} prompts need {len(batches) - 1} boundaries, got {n}")
+    return batches, batches[0]
+
+
+def _timeline_row_plan(plan, boundaries, transition):
+    """The row plan of `plan` under a timeline with these boundaries (windows.prompt_weights, windows.row_plan): host only, refuses
+    early."""
+    from .windows import prompt_weights, row_plan
+    return row_plan(plan, prompt_weights(plan.T, [] if boundaries is None else list(boundaries), transition))
+
+
+def timeline_frames(timeline, per_second, latent_t):
+    """Pure host: a timeline [(start_s, prompt) | (start_s, prompt, transcription), ...] in seconds -> (prompts, transcriptions,
+    the K-1 boundaries in latent frames = start_s * per_second, possibly fractional).  The first start must be 0, the starts must
+    ascend and lie before the clip's end.  A start that is a whole frame in exact arithmetic (5 s at 25.6 frames per second) is
+    that frame: anything within 1e-9 of a whole frame is snapped to it.  ValueError otherwise."""
+    entries = list(timeline) if timeline is not None else []
+    if not entries:
+        raise ValueError("timeline: at least one entry (start_s, prompt)")
+    prompts, transcriptions, starts = [], [], []
+    for e in entries:
+        if not isinstance(e, (list, tuple)) or len(e) not in (2, 3) or not isinstance(e[1], str) \
+                or (len(e) == 3 and not isinstance(e[2], str)):
+            raise ValueError(f"timeline: an entry is (start_s, prompt) or (start_s, prompt, transcription), got {e!r}")
+        try:
+            t0 = float(e[0])
+        except (TypeError, ValueError):
+            raise ValueError(f"timeline: a start must be a number of seconds, got {e[0]!r}")
+        if not np.isfinite(t0):
+            raise ValueError(f"timeline: a start must be finite, got {e[0]!r}")
+        starts.append(t0)
+        prompts.append(e[1])
+        transcriptions.append(e[2] if len(e) == 3 else "")
+    if starts[0] != 0.0:
+        raise ValueError(f"timeline: the first entry must start at 0 s, got {starts[0]!r}")
+    boundaries = []
+    for t0 in starts[1:]:
+        b = t0 * float(per_second)
+        if abs(b - round(b)) < 1e-9:
+            b = float(round(b))
+        if not 0.0 < b < latent_t or (boundaries and b <= boundaries[-1]):
+            raise ValueError(f"timeline: the starts must ascend strictly inside (0, {latent_t / float(per_second):g}) s, got {starts!r}")
+        boundaries.append(b)
+    return prompts, transcriptions, boundaries
+
+
 def resolve_sampler(sampler, use_plms=False):
     """The `sampler=` keyword of sample_log / generate_batch / generate_batch_masked / text_to_audio /
     super_resolution_and_inpainting: None (the reference's behaviour) or a name in SAMPLERS, not together with use_plms=True."""
@@ -1027,15 +1091,25 @@ class LatentDiffusion(nn.Module):
     @torch.no_grad()
     def generate_batch_long(self, batch, latent_t_size, hop=None, ddim_steps=200, ddim_eta=1.0, unconditional_guidance_scale=1.0,
                             unconditional_conditioning=None, use_plms=False, sampler=None, negative_prompt=None,
-                            guidance_rescale=0.0, n_gen=1, shard=None, loop=False):
+                            guidance_rescale=0.0, n_gen=1, shard=None, loop=False, boundaries=None, transition=0.0):
         """Long-form text-to-audio by windowed diffusion (MultiDiffusion, Bar-Tal et al. 2023): ONE long latent of
         `latent_t_size` frames; at every step the UNet runs on overlapping windows of `self.latent_t_size` frames — the trained
         length, `hop` frames apart (default 3*Tw//4) — in one pass over W*b rows, the windows' outputs are fused by a tapered,
         normalised overlap-add (ops.window_gather / ops.window_merge, two nodes of the replayed step graph) and the sampler
         steps the long latent.  The VAE decodes the final latent window by window, the mels are cross-faded by the same merge
         kernel on the plan scaled to mel frames, and the vocoder runs once over the long mel.  UNet and VAE only ever see their
-        trained shape.  All windows share one conditioning: right for ambience, textures and music, wrong for a transcription
-        that should advance through the clip.  `sampler`, `negative_prompt` and `guidance_rescale` as in generate_batch.
+        trained shape.  With one batch all windows share one conditioning: right for ambience, textures and music, wrong for a
+        scene or a transcription that should advance through the clip — that is a prompt timeline, below.  `sampler`,
+        `negative_prompt` and `guidance_rescale` as in generate_batch.
+
+        A prompt timeline: `batch` a LIST of K batches of equal B0, one per prompt in timeline order, `boundaries`
+        the K-1 latent frames (possibly fractional) where prompt k takes over from k-1, `transition` the width of the cross-fade
+        round every boundary, in latent frames (0: a hard cut).  The prompt weights follow the timeline frame by frame
+        (windows.prompt_weights); a window that sees several prompts runs once under each (windows.row_plan: R rows >= W windows,
+        one UNet pass over R*b rows, 2*R*b under guidance with the unconditional / negative conditioning tiled R times), and
+        the rows are fused per frame by taper times prompt weight (ops.window_merge on the row plan).  The tail is unchanged:
+        it runs on the plan without rows, the decode does not depend on prompts.  K = 1 is the run without a timeline, bit for
+        bit.  The negative prompt and the (R1) shape are those of the first batch.  Not together with loop=True.
 
         `loop=True`: a clip that loops without a seam.  Sampling runs on the RING plan of the same numbers
         (long_form_plans(..., ring=True)): the window starts are spread round a circle of `latent_t_size` frames and windows wrap
@@ -1048,13 +1122,18 @@ class LatentDiffusion(nn.Module):
 
         Refused before any draw or GPU work: ddim_steps=None (the ancestral sampler has no windowed form), n_gen != 1 (the CLAP
         re-ranker scores clips of the trained length), shard=, a length that is no multiple of 8 or shorter than the window, more
-        than 32 windows; with loop=True also a hop of the whole window (no overlap: nothing would denoise across the junction).
+        than 32 windows; with loop=True also a hop of the whole window (no overlap: nothing would denoise across the junction);
+        with a timeline also loop=True, batches of unequal size, a count of boundaries other than K-1, and what
+        windows.prompt_weights / windows.row_plan refuse (boundaries, transition, a prompt without a frame, more than 64 rows).
 
         Host-generator order (RNG contract R): (R1) randn(B0, C, h, w) of the batch's mel, drawn and discarded
         exactly as generate_batch does; (R1b) the rand(1) of _cfg_dropout_draw on every call but an object's first; the
         conditioners' draws (twice with a negative prompt); randn(B0, C, latent_t_size, F), the long x_T; the sampler's per-step
         draws at that long shape (DDIM one per step, PLMS one per step and one more in its first, DPM-Solver++ none).  loop=True
-        draws exactly what the linear job draws, in the same order: a ring changes which frames a window sees, not a draw."""
+        draws exactly what the linear job draws, in the same order: a ring changes which frames a window sees, not a draw.  A
+        timeline: the conditioners' draws come once per prompt, in timeline order, then the negative prompt's; everything else
+        is unchanged."""
+        batches, batch = _timeline_batches(batch, boundaries, loop, "generate_batch_long")
         if shard is not None:
             raise ValueError("generate_batch_long: shard= is not supported on this path")
         if ddim_steps is None:
@@ -1067,19 +1146,25 @@ class LatentDiffusion(nn.Module):
         neg_batch, guidance_rescale = _guidance_kwargs(dict(kw, guidance_rescale=guidance_rescale), unconditional_guidance_scale,
                                                        batch, ddim_steps)
         plan, mel_plan = self.long_form_plans(latent_t_size, hop, ring=loop)
+        run_plan = plan if batches is None else _timeline_row_plan(plan, boundaries, transition)   # refuses, host only
         fb = batch["log_mel_spec"] if self.first_stage_key == "fbank" else batch[self.first_stage_key]
         B0 = fb.shape[0]
         f = 2 ** (self.first_stage_model.encoder.num_resolutions - 1)
         torch.randn((B0, self.first_stage_model.embed_dim, fb.shape[-2] // f, fb.shape[-1] // f))  # (R1) draw & discard
         self._cfg_dropout_draw()                                                                     # (R1b) every call but the first
-        c = self.get_learned_conditioning_dict(batch)
+        c = self._timeline_cond(batches) if batches is not None else self.get_learned_conditioning_dict(batch)
         unconditional_conditioning = _unconditional_half(self, neg_batch, 1, B0, unconditional_guidance_scale,
                                                          unconditional_conditioning)
         samples, _ = self.sample_log(cond=c, batch_size=B0, x_T=None, ddim=True, ddim_steps=ddim_steps, eta=ddim_eta,
                                      unconditional_guidance_scale=unconditional_guidance_scale,
-                                     unconditional_conditioning=unconditional_conditioning, use_plms=use_plms, windows=plan,
+                                     unconditional_conditioning=unconditional_conditioning, use_plms=use_plms, windows=run_plan,
                                      **_sample_log_keywords(sampler, guidance_rescale))
         return self._long_tail(samples, plan, mel_plan, batch)
+
+    def _timeline_cond(self, batches):
+        """The conditioners on every prompt of a timeline, in timeline order (the order of their host-generator draws)."""
+        from .windows import PerPrompt
+        return PerPrompt([self.get_learned_conditioning_dict(b) for b in batches])
 
     def _long_tail(self, samples, plan, mel_plan, batch):
         """The tail of a long-form job: the VAE at its trained shape on the W*B0 windows of the final latent, the mels cross-faded
@@ -1132,7 +1217,7 @@ class LatentDiffusion(nn.Module):
     @torch.no_grad()
     def generate_batch_long_from_audio(self, batch, latent_t_size, keep, hop=None, ddim_steps=200, ddim_eta=1.0,
                                        unconditional_guidance_scale=1.0, use_plms=False, sampler=None, negative_prompt=None,
-                                       guidance_rescale=0.0, n_gen=1, shard=None, loop=False):
+                                       guidance_rescale=0.0, n_gen=1, shard=None, loop=False, boundaries=None, transition=0.0):
         """Continuation and inpainting of long clips: generate_batch_long around a source.  `batch["log_mel_spec"]`
         is the long mel [B0, latent_t_size*f, F_mel] of the source; `keep` lists the half-open latent-frame intervals [a, b) to
         keep (windows.keep_mask); everything else is generated under the prompt.  The source is encoded window by window
@@ -1148,14 +1233,20 @@ class LatentDiffusion(nn.Module):
         periodic — sampling runs on the ring plan with that source (windows.with_source keeps the flag) and the tail is
         generate_batch_long's ring tail.  `keep` means what it means without it; the draws and their order do not change.
 
+        A prompt timeline, as in generate_batch_long: `batch` a list of K batches (the FIRST one carries the source's
+        mel), `boundaries`, `transition`; the source rides on the row plan, the blend writes every covering row
+        (aldm_window_blend_gather_rows).  Not together with loop=True.
+
         Refused before any draw or GPU work: ddim_steps=None, n_gen != 1, shard=, bad lengths or hops (long_form_plans), a bad
-        `keep`, a mel whose length is not latent_t_size*f.
+        `keep`, a mel whose length is not latent_t_size*f, a bad timeline (generate_batch_long).
 
         Host-generator order (RNG contract R): (R1) randn(B0, C, latent_t_size, F) at the LONG shape, the
         posterior noise, really used; (R1b) the rand(1) of _cfg_dropout_draw on every call but an object's first; the
         conditioners' draws (twice with a negative prompt); randn(B0, C, latent_t_size, F), the long x_T; per step at the long
-        shape: DDIM the q-noise then the step noise, PLMS the q-noise then its own draws, DPM-Solver++ the q-noise only."""
+        shape: DDIM the q-noise then the step noise, PLMS the q-noise then its own draws, DPM-Solver++ the q-noise only.  A timeline:
+        the conditioners' draws once per prompt in timeline order, then the negative prompt's."""
         from .windows import keep_mask, with_source
+        batches, batch = _timeline_batches(batch, boundaries, loop, "generate_batch_long_from_audio")
         if shard is not None:
             raise ValueError("generate_batch_long_from_audio: shard= is not supported on this path")
         if ddim_steps is None:
@@ -1170,6 +1261,7 @@ class LatentDiffusion(nn.Module):
         plan, mel_plan = self.long_form_plans(latent_t_size, hop)
         ring_plans = self.long_form_plans(latent_t_size, hop, ring=True) if loop else None   # refuses a bad ring before any draw
         mask_t = keep_mask(plan.T, keep)
+        run_plan = plan if batches is None else _timeline_row_plan(plan, boundaries, transition)   # refuses, host only
         fb = batch["log_mel_spec"] if self.first_stage_key == "fbank" else batch[self.first_stage_key]
         f = 2 ** (self.first_stage_model.encoder.num_resolutions - 1)
         if fb.dim() != 3 or fb.shape[-2] != plan.T * f or fb.shape[-1] % f != 0:
@@ -1178,16 +1270,17 @@ class LatentDiffusion(nn.Module):
         B0 = fb.shape[0]
         n_post = torch.randn((B0, self.first_stage_model.embed_dim, plan.T, fb.shape[-1] // f))   # (R1) the posterior draw, long
         self._cfg_dropout_draw()                                                                    # (R1b) every call but the first
-        c = self.get_learned_conditioning_dict(batch)
+        c = self._timeline_cond(batches) if batches is not None else self.get_learned_conditioning_dict(batch)
         unconditional_conditioning = _unconditional_half(self, neg_batch, 1, B0, unconditional_guidance_scale)
         z = self.encode_long(fb.unsqueeze(1).float().contiguous().to(self.device), plan, mel_plan, n_post.to(self.device))
         self.last_long_source = z
         if loop:   # the source was encoded on the linear plans; sampling and the tail run on the ring
             plan, mel_plan = ring_plans
+            run_plan = plan   # no timeline on a ring (_timeline_batches)
         samples, _ = self.sample_log(cond=c, batch_size=B0, x_T=None, ddim=True, ddim_steps=ddim_steps, eta=ddim_eta,
                                      unconditional_guidance_scale=unconditional_guidance_scale,
                                      unconditional_conditioning=unconditional_conditioning, use_plms=use_plms,
-                                     windows=with_source(plan, z, mask_t), **_sample_log_keywords(sampler, guidance_rescale))
+                                     windows=with_source(run_plan, z, mask_t), **_sample_log_keywords(sampler, guidance_rescale))
         return self._long_tail(samples, plan, mel_plan, batch)
 
 
@@ -1442,7 +1535,7 @@ def text_to_audio(latent_diffusion, text, transcription="", seed=42, ddim_steps=
 
 
 def text_to_audio_long(latent_diffusion, text, duration, overlap=2.5, transcription="", seed=42, ddim_steps=200, guidance_scale=3.5,
-                       sampler=None, negative_prompt=None, guidance_rescale=0.0, loop=False):
+                       sampler=None, negative_prompt=None, guidance_rescale=0.0, loop=False, timeline=None, transition=0.0):
     """Long-form text-to-audio: a clip of `duration` seconds — longer than the model's trained length — by windowed diffusion
     (LatentDiffusion.generate_batch_long): the UNet and the VAE work on windows of the model's `latent_t_size` frames that overlap
     by `overlap` seconds, fused at every step.  latent_t_size = int(duration * latent_t_per_second) must be a multiple of 8 and
@@ -1451,17 +1544,52 @@ def text_to_audio_long(latent_diffusion, text, duration, overlap=2.5, transcript
     transcription does not advance through the clip.  `sampler`, `negative_prompt`, `guidance_rescale` as in text_to_audio.  The
     model's own latent_t_size is not changed.  `loop=True`: a clip whose last sample runs into its first — windowed diffusion
     on a ring (generate_batch_long(..., loop=True)); `duration` may then equal the trained length, and `overlap` must be
-    positive (a ring without overlap has nothing across its junction).  Returns np.float32 [1, 1, samples]."""
+    positive (a ring without overlap has nothing across its junction).
+
+    `timeline`: a scene that advances — [(0.0, "rain"), (12.0, "thunder"), (24.0, "birds after rain")], entries
+    (start_s, prompt) or (start_s, prompt, transcription), the first at 0 s; `text` must then be None (and `transcription` empty).
+    Prompt k sounds from its start to the next one's, cross-faded over `transition` seconds round every start (0: hard cuts);
+    seconds become latent frames by latent_t_per_second (timeline_frames).  A window that sees several prompts runs once under
+    each, so the UNet pass grows from W to R rows (generate_batch_long).  Not together with loop=True.
+    Returns np.float32 [1, 1, samples]."""
     sampler_kw = _sampler_kwargs(sampler, negative_prompt, guidance_rescale)
     per_second = float(latent_diffusion.latent_t_per_second)
     latent_t = int(duration * per_second)
     hop = latent_diffusion.latent_t_size - int(round(overlap * per_second))
+    tl_kw, make = _timeline_entry(latent_diffusion, text, transcription, timeline, transition, loop, latent_t, hop, ddim_steps,
+                                   "text_to_audio_long")
     latent_diffusion.long_form_plans(latent_t, hop, ring=loop)   # refuse before any GPU work
     seed_everything(int(seed))
-    batch = make_batch_for_text_to_audio(text, transcription=transcription, batchsize=1)
+    batch = make()
     with torch.no_grad():
         return latent_diffusion.generate_batch_long(batch, latent_t, hop=hop, unconditional_guidance_scale=guidance_scale,
-                                                    ddim_steps=ddim_steps, loop=loop, **sampler_kw)
+                                                    ddim_steps=ddim_steps, loop=loop, **sampler_kw, **tl_kw)
+
+
+def _timeline_entry(latent_diffusion, text, transcription, timeline, transition, loop, latent_t, hop, ddim_steps, who):
+    """The `text` / `timeline` / `transition` arguments of text_to_audio_long and extend_audio -> (the keywords the timeline adds to
+    generate_batch_long*, a callable making the batch — or the list of batches — after the seed is set).  Without a timeline: ({},
+    today's batch).  Everything a timeline can be refused for is refused here, on the host."""
+    if timeline is None:
+        if transition != 0.0:
+            raise ValueError(f"{who}: transition= needs a timeline")
+        return {}, lambda: make_batch_for_text_to_audio(text, transcription=transcription, batchsize=1)
+    if text is not None or transcription:
+        raise ValueError(f"{who}: with timeline= the prompts (and transcriptions) are the timeline's: pass text=None")
+    if loop:
+        raise ValueError(f"{who}: a prompt timeline together with loop=True is not supported (a ring has no first prompt)")
+    if ddim_steps is None:
+        raise ValueError(f"{who} needs ddim_steps: the ancestral sampler has no windowed form")
+    per_second = float(latent_diffusion.latent_t_per_second)
+    prompts, transcriptions, boundaries = timeline_frames(timeline, per_second, latent_t)
+    try:
+        tau = float(transition) * per_second
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: transition must be a number of seconds, got {transition!r}")
+    plan, _ = latent_diffusion.long_form_plans(latent_t, hop)
+    _timeline_row_plan(plan, boundaries, tau)   # refuse before any draw
+    return ({"boundaries": boundaries, "transition": tau},
+            lambda: [make_batch_for_text_to_audio(p, transcription=t, batchsize=1) for p, t in zip(prompts, transcriptions)])
 
 
 def _source_seconds(source):
@@ -1491,7 +1619,8 @@ def keep_frames(keep, per_second, latent_t):
 
 
 def extend_audio(latent_diffusion, text, original_audio_file_path, duration, keep=None, overlap=2.5, transcription="", seed=42,
-                 ddim_steps=200, guidance_scale=3.5, sampler=None, negative_prompt=None, guidance_rescale=0.0, loop=False):
+                 ddim_steps=200, guidance_scale=3.5, sampler=None, negative_prompt=None, guidance_rescale=0.0, loop=False,
+                 timeline=None, transition=0.0):
     """Continue or inpaint a long clip: a clip of `duration` seconds — longer than the model's trained length — that keeps parts
     of the recording `original_audio_file_path` (a path, or a 1-D float waveform at 16 kHz; zero-padded or cut to `duration`) and
     generates the rest under the prompt `text` by windowed diffusion (LatentDiffusion.generate_batch_long_from_audio).  `keep`
@@ -1504,6 +1633,7 @@ def extend_audio(latent_diffusion, text, original_audio_file_path, duration, kee
     region is not pasted back at the end (see generate_batch_long_from_audio).  The model's own latent_t_size is not changed.
     `loop=True`: the generated part runs back into the source's beginning, so the whole clip loops ("make my 8 seconds loop by
     generating a 4-second bridge": duration=12, the default keep); `overlap` must then be positive.
+    `timeline` / `transition`: a prompt timeline for the generated part, as in text_to_audio_long (`text` must then be None).
     Returns np.float32 [1, 1, samples]."""
     from .stft import TacotronSTFT
     from .windows import keep_mask
@@ -1518,6 +1648,8 @@ def extend_audio(latent_diffusion, text, original_audio_file_path, duration, kee
     latent_diffusion.long_form_plans(latent_t, hop)   # refuse before any GPU work
     if loop:
         latent_diffusion.long_form_plans(latent_t, hop, ring=True)
+    tl_kw, make = _timeline_entry(latent_diffusion, text, transcription, timeline, transition, loop, latent_t, hop, ddim_steps,
+                                   "extend_audio")
     f = 2 ** (latent_diffusion.first_stage_model.encoder.num_resolutions - 1)
     mel_bins = int(latent_diffusion.latent_f_size) * f
     if int(latent_diffusion.sampling_rate) != 16000 or mel_bins != 64:
@@ -1530,12 +1662,13 @@ def extend_audio(latent_diffusion, text, original_audio_file_path, duration, kee
     seed_everything(int(seed))
     fn_STFT = TacotronSTFT(1024, 160, 1024, 64, 16000, 0, 8000)  # utils.py:262-270 "preprocessing"
     mel, _, _ = wav_to_fbank(original_audio_file_path, target_length=latent_t * f, fn_STFT=fn_STFT)
-    batch = make_batch_for_text_to_audio(text, transcription=transcription, batchsize=1)
-    batch["log_mel_spec"] = batch["fbank"] = mel[None, ...].float().cpu()
+    batch = make()
+    first = batch[0] if timeline is not None else batch   # the source's mel rides on the (first) batch
+    first["log_mel_spec"] = first["fbank"] = mel[None, ...].float().cpu()
     with torch.no_grad():
         return latent_diffusion.generate_batch_long_from_audio(batch, latent_t, frames, hop=hop,
                                                                unconditional_guidance_scale=guidance_scale,
-                                                               ddim_steps=ddim_steps, loop=loop, **sampler_kw)
+                                                               ddim_steps=ddim_steps, loop=loop, **sampler_kw, **tl_kw)
 
 
 def audio_to_audio(latent_diffusion, text, original_audio_file_path, strength=0.5, transcription="", seed=42,

@@ -394,7 +394,24 @@ class SamplerBase(object):
         ops.window_blend_gather takes the gather's place — it blends q_sample(x0, t) into x IN PLACE where the mask is 1, with the
         q-noise row and the coefficient row the device-side `win.step_idx` selects from `win.qnoise` and `win.blend_coef`, and
         writes the windows of the blended latent.  Any further pass of the same step (PLMS's second one in its eager step 0, on the
-        provisional x_prev) gathers plainly.  The sampler sets win.qnoise and win.step_idx before its first step."""
+        provisional x_prev) gathers plainly.  The sampler sets win.qnoise and win.step_idx before its first step.
+
+        A row plan (windows.row_plan, a prompt timeline): the same three launches in their `_rows` forms over
+        win.n = plan.R rows — one per (window, prompt) pair, cond holding every row's own prompt (windows.rows_cond), uncond tiled
+        R times — and the merge reads the per-row, per-frame weights from win.wr, a static [R, Tw] device buffer (eager passes into
+        fresh tensors, `static=False`, read the same buffer).  plan_run is where a row plan and a PerPrompt are matched; here `cond` is
+        normally its per-row result.  A PerPrompt that reaches this function is expanded with windows.rows_cond when win.plan has rows
+        and refused (ValueError) when it has none or the prompt counts differ; a row plan without win.wr / win.n == R is refused too."""
+        from .windows import PerPrompt, has_rows, rows_cond
+        rows = win is not None and has_rows(win.plan)
+        if isinstance(cond, PerPrompt):
+            # plan_run hands the per-row conditioning on; a caller with a hand-made `win` may pass the PerPrompt itself
+            if not rows:
+                raise ValueError("model_output: a PerPrompt conditioning needs a row plan (windows.row_plan) on `win`")
+            cond = rows_cond(cond, win.plan)   # refuses a wrong number of prompts
+        if rows and (getattr(win, "wr", None) is None or getattr(win, "n", None) != win.plan.R):
+            raise ValueError("model_output: a row plan needs win.n == plan.R and win.wr, the [R, Tw] merge weights on the device "
+                             "(plan_run builds both)")
         if win is not None:
             if win.blend and first_pass:
                 # a plan with a source: the blend of the known region on the long latent, in place, and the gather are one launch
@@ -402,8 +419,8 @@ class SamplerBase(object):
                                              out=win.xw if static else None)
             else:
                 xw = ops.window_gather(x, win.plan, out=win.xw if static else None)
-            eps_w = self.model_output(xw, t_row, win.plan.W * b, cond, uncond, use_cfg, prepared)
-            return ops.window_merge(eps_w.contiguous(), win.plan, out=win.merged if static else None)
+            eps_w = self.model_output(xw, t_row, win.n * b, cond, uncond, use_cfg, prepared)
+            return ops.window_merge(eps_w.contiguous(), win.plan, out=win.merged if static else None, weights=win.wr)
         if not use_cfg:
             return self.model.apply_model(x, t_row[:b].long(), cond).contiguous()
         if hasattr(self.model, "apply_model_cfg"):
@@ -420,7 +437,10 @@ class SamplerBase(object):
         the per-step noise keep the long shape; `p.cond` / `p.uncond` are the conditionings tiled W times (window-major), t_tab
         has W times the columns, prepare_cfg sees the tiled pair, and `p.win` holds the plan and the two static window buffers
         of model_output (xw [W*b, C, Tw, F], merged [2, b, ...] or [b, ...]).  Without a plan p.cond / p.uncond are the arguments
-        and p.win is None.  Not together with mask / x0: a source to keep rides on the plan (windows.with_source) and fills
+        and p.win is None.  A row plan (windows.row_plan): `cond` must be a windows.PerPrompt of its K conditionings (and a
+        PerPrompt needs a row plan; ValueError otherwise); R = plan.R takes W's place for t_tab, xw and the tiled uncond, p.cond is
+        windows.rows_cond (row r under its own prompt), and p.win.wr holds the merge weights on the device.
+        Not together with mask / x0: a source to keep rides on the plan (windows.with_source) and fills
         p.mask_d / p.x0_d / p.blend_coef as a mask does, with p.win.blend set — the blend then runs inside the step, fused with
         the gather (model_output), not between the steps.
 
@@ -434,13 +454,15 @@ class SamplerBase(object):
         in this order: img, coef, t_tab, mask_d, x0_d, blend_coef, then the model's prepare_cfg."""
         dev = torch.device("cuda")
         shape = tuple(shape)
+        from .windows import check_per_prompt, has_rows
+        check_per_prompt(cond, windows)   # a row plan and a PerPrompt conditioning go together, or neither
         W, source = 1, None
         if windows is not None:
             if mask is not None or x0 is not None:
                 raise ValueError("windows= together with mask / x0: inpainting over windows is not supported")
             if len(shape) != 4 or shape[2] != windows.T:
                 raise ValueError(f"windows= is a plan over T={windows.T} frames, the latent shape is {shape}")
-            W = windows.W
+            W = windows.R if has_rows(windows) else windows.W   # the UNet's row groups: rows of a timeline, else windows
             if getattr(windows, "x0", None) is not None:
                 # a source rides on the plan (windows.with_source): inpainting / continuation over windows
                 if tuple(windows.x0.shape) != shape:
@@ -476,15 +498,19 @@ class SamplerBase(object):
             p.blend_coef = torch.stack([self.sqrt_alphas_cumprod[tr], self.sqrt_one_minus_alphas_cumprod[tr]],
                                        1).contiguous().to(dev)  # [S, 2] = {sqrt(abar_t), sqrt(1 - abar_t)}
         if windows is not None:
-            from .windows import tile_cond
-            p.cond, p.uncond = tile_cond(cond, W), tile_cond(unconditional_conditioning, W)
+            from .windows import rows_cond, tile_cond
+            p.cond = rows_cond(cond, windows) if has_rows(windows) else tile_cond(cond, W)
+            p.uncond = tile_cond(unconditional_conditioning, W)
             b, C, _, F = shape
             # blend: the plan carries a source; the fused blend-and-gather node reads x0 / mask / blend_coef from here and the
             # q-noise table and the step counter the sampler puts next to them (model_output)
             p.win = SimpleNamespace(plan=windows, xw=torch.empty((W * b, C, windows.Tw, F), device=dev, dtype=torch.float32),
                                     merged=torch.empty(((2,) if use_cfg else ()) + shape, device=dev, dtype=torch.float32),
                                     blend=source is not None, x0=p.x0_d, mask=p.mask_d, blend_coef=p.blend_coef, qnoise=None,
-                                    step_idx=None)
+                                    step_idx=None, n=W,
+                                    # a row plan: the merge's [R, Tw] weights, a static buffer of the run (of the step graph's
+                                    # cache entry, which refills it per job: two timelines of one row geometry share a graph)
+                                    wr=windows.wr.to(dev).contiguous() if has_rows(windows) else None)
         if use_cfg and hasattr(self.model, "apply_model_cfg") and hasattr(self.model, "prepare_cfg"):
             p.prepared = self.model.prepare_cfg(p.cond, p.uncond)
         return p

@@ -7,6 +7,10 @@ kernels need: the window starts and the normalised weights.
 
 A plan may carry a source to keep (`with_source`, `keep_mask`): continuation and inpainting of long clips.  The
 samplers then blend q_sample(source, t) into the long latent in front of every step's gather (ops.window_blend_gather).
+
+A linear plan may carry a prompt timeline (`prompt_weights`, `row_plan`, `PerPrompt`, `rows_cond`): every prompt has a
+weight per latent frame, a window that sees several prompts becomes one ROW per prompt, the UNet runs on the rows — each under its
+own prompt's conditioning — and the rows are fused per frame by taper times prompt weight (the `_rows` forms of the three launches).
 """
 from __future__ import annotations
 
@@ -115,8 +119,166 @@ def _ring_plan(T, Tw, hop, scale):
 
 def plan_key(plan):
     """What identifies a plan's launch sequence (the starts are kernel arguments captured with a step graph; a ring plan launches
-    the wrap-around kernels, so a ring and a linear plan never share a step graph)."""
+    the wrap-around kernels, so a ring and a linear plan never share a step graph).  A row plan (row_plan, prompt timelines) launches
+    the row kernels with its row starts: (T, Tw, row_starts, "rows"), distinct from every linear and ring key — its weights are NOT
+    part of the key: they live in a static buffer of the step graph's cache entry, refilled per job."""
+    if has_rows(plan):
+        return (plan.T, plan.Tw, tuple(plan.row_starts), "rows")
     return (plan.T, plan.Tw, tuple(plan.starts), bool(getattr(plan, "ring", False)))
+
+
+# ---- prompt timelines (DESIGN.md §9h): per-frame prompt weights, rows = (window, prompt) pairs -----------------------------------------
+MAX_ROWS = 64   # the size of `aldm_window_rows` (include/aldm_hip.h)
+
+
+def has_rows(plan):
+    """True for a row plan (row_plan): its launches are the `_rows` kernels and its UNet pass has plan.R row groups, not plan.W."""
+    return getattr(plan, "rows", None) is not None
+
+
+def prompt_weights(T, boundaries, transition=0.0):
+    """The prompt weights m [K, T] (numpy fp64) of a timeline of K = len(boundaries) + 1 prompts over T latent frames: prompt k
+    sounds between the boundaries beta_k and beta_{k+1} (latent frames, possibly fractional, ascending, inside (0, T)) and cross-fades
+    into its neighbours over `transition` frames centred on the boundary.  With frame centres t + 0.5:
+
+      u_0 = 1, u_K = 0, u_k(t) = clip((t + 0.5 - beta_k) / transition + 0.5, 0, 1)   (transition == 0: 1 if t + 0.5 >= beta_k else 0)
+      m_k = u_k - u_{k+1}
+
+    non-negative, summing to 1 over k at every frame, exactly 1.0 or 0.0 outside the transitions.  ValueError: T not a positive
+    integer, boundaries not finite, not strictly ascending or outside (0, T), a negative or non-finite transition, a prompt whose
+    weight is zero at every frame (two boundaries with no frame centre between them and a transition too short to reach one)."""
+    T = _check_int(T, "T")
+    if T <= 0:
+        raise ValueError(f"prompt_weights: T must be positive, got {T}")
+    try:
+        beta = [float(b) for b in boundaries]
+        tau = float(transition)
+    except (TypeError, ValueError):
+        raise ValueError(f"prompt_weights: boundaries and transition must be numbers (latent frames), got {boundaries!r}, {transition!r}")
+    if not np.isfinite(tau) or tau < 0.0:
+        raise ValueError(f"prompt_weights: transition must be finite and >= 0 latent frames, got {transition!r}")
+    for i, b in enumerate(beta):
+        if not np.isfinite(b) or not 0.0 < b < T:
+            raise ValueError(f"prompt_weights: a boundary must lie inside (0, T={T}), got {b!r}")
+        if i > 0 and b <= beta[i - 1]:
+            raise ValueError(f"prompt_weights: boundaries must ascend strictly, got {beta!r}")
+    K = len(beta) + 1
+    centre = np.arange(T, dtype=np.float64) + 0.5
+    u = np.zeros((K + 1, T), dtype=np.float64)
+    u[0] = 1.0
+    for k, b in enumerate(beta, start=1):
+        u[k] = np.clip((centre - b) / tau + 0.5, 0.0, 1.0) if tau > 0.0 else (centre >= b).astype(np.float64)
+    m = u[:-1] - u[1:]
+    assert float(m.min()) >= 0.0
+    for k in range(K):
+        if not np.any(m[k] != 0.0):
+            raise ValueError(f"prompt_weights: prompt {k} has no frame: its weight is zero over all T={T} frames (boundaries "
+                             f"{beta!r}, transition {tau})")
+    return m
+
+
+def row_plan(plan, m):
+    """The row plan of a linear window plan under the prompt weights `m` [K, T] (prompt_weights).  A ROW is a pair
+    (window j, prompt k) with m_k != 0 somewhere inside window j, ordered by j, then k: the UNet runs once per row, under the row's
+    prompt, and the rows are fused per latent frame.  -> an object with the base plan's fields (T, Tw, hop, scale, W, starts, ring,
+    wn — and x0 / mask of a plan with a source) plus
+
+      base        the plan without rows (no prompts enter the window-wise VAE tail, which runs on it); a source stays on the row plan
+      rows        ((j, k), ...);  R = len(rows) <= 64
+      row_starts  s_j of every row: non-decreasing, equal starts = one window under several prompts
+      row_prompt  k of every row
+      wr          [R, Tw] fp32: taper_j[p] * m_k[s_j + p] divided by the sum of that product over every row on the frame, in fp64,
+                  rounded to fp32 once.  Over every frame the rows' weights sum to 1; where one row alone has weight on a frame wr is
+                  exactly 1.0, where the row's prompt is silent exactly 0.0; K == 1: wr == plan.wn bitwise and row_starts == starts
+      cover       the largest number of rows with non-zero weight on one frame
+
+    ValueError: a ring plan, m not [K, plan.T], negative or not summing to 1, a prompt with no frame, more than 64 rows."""
+    if getattr(plan, "ring", False):
+        raise ValueError("row_plan: a ring plan cannot carry a timeline (a loop has no first prompt); use a linear window_plan")
+    if has_rows(plan):
+        raise ValueError("row_plan: the plan already has rows; build them from its base plan")
+    m = np.asarray(m.detach().cpu().numpy() if torch.is_tensor(m) else m, dtype=np.float64)
+    if m.ndim != 2 or m.shape[0] < 1 or m.shape[1] != plan.T:
+        raise ValueError(f"row_plan: m must be [K, T={plan.T}] prompt weights, got {m.shape}")
+    if not np.all(np.isfinite(m)) or float(m.min()) < 0.0 or float(np.abs(m.sum(0) - 1.0).max()) > 1e-9:
+        raise ValueError("row_plan: prompt weights must be finite, non-negative and sum to 1 at every frame (prompt_weights)")
+    K, T, Tw = m.shape[0], plan.T, plan.Tw
+    for k in range(K):
+        if not np.any(m[k] != 0.0):
+            raise ValueError(f"row_plan: prompt {k} has no frame: its weight is zero over all T={T} frames")
+    rows = [(j, k) for j, s in enumerate(plan.starts) for k in range(K) if np.any(m[k, s:s + Tw] != 0.0)]
+    if len(rows) > MAX_ROWS:
+        raise ValueError(f"row_plan: {len(rows)} rows (windows under prompts), at most {MAX_ROWS}: use fewer prompts, a shorter "
+                         "transition or a larger hop")
+    # the raw taper of window_plan, on the plan's own (scaled) numbers.  Numerators taper * m, the denominator their sum over the
+    # rows in row order: with K == 1 the numerators are the tapers and the sums window_plan's own, term for term, so wr == wn bitwise
+    p = np.arange(Tw, dtype=np.float64)
+    ramp = Tw - plan.hop
+    w = np.minimum(1.0, np.minimum((p + 1.0) / (ramp + 1.0), (Tw - p) / (ramp + 1.0)))
+    num = [w * m[k, plan.starts[j]:plan.starts[j] + Tw] for j, k in rows]
+    norm = np.zeros(T, dtype=np.float64)
+    count = np.zeros(T, dtype=np.int64)
+    for (j, k), a in zip(rows, num):
+        s = plan.starts[j]
+        norm[s:s + Tw] += a
+        count[s:s + Tw] += a != 0.0
+    assert float(norm.min()) > 0.0 and int(count.min()) >= 1
+    wr64 = np.stack([a / norm[plan.starts[j]:plan.starts[j] + Tw] for (j, k), a in zip(rows, num)])
+    for r, (j, k) in enumerate(rows):
+        s = plan.starts[j]
+        # one row alone on a frame: a / a, exactly 1; a silent prompt: 0 / norm, exactly 0 (the merge kernel's skip rests on it)
+        assert np.all(wr64[r][(count[s:s + Tw] == 1) & (num[r] != 0.0)] == 1.0) and np.all(wr64[r][num[r] == 0.0] == 0.0)
+    wr = torch.from_numpy(wr64.astype(np.float32)).contiguous()
+    if K == 1:
+        assert torch.equal(wr, plan.wn)
+    fields = {k: v for k, v in plan.__dict__.items() if not k.startswith("_")}
+    base = SimpleNamespace(**{k: v for k, v in fields.items() if k not in ("x0", "mask")})
+    return SimpleNamespace(**dict(fields, base=base, rows=tuple(rows), R=len(rows), row_starts=tuple(plan.starts[j] for j, _ in rows),
+                                  row_prompt=tuple(k for _, k in rows), wr=wr, cover=int(count.max())))
+
+
+class PerPrompt:
+    """K conditionings, one per prompt of a timeline, in timeline order: the `cond` of a sampler run over a row plan.  A marker class:
+    a conditioning is already a tuple, list or dict of tensors in this code base, so a bare list of them would be ambiguous."""
+
+    def __init__(self, conds):
+        conds = list(conds)
+        if not conds:
+            raise ValueError("PerPrompt: at least one conditioning")
+        self.conds = conds
+
+    def __len__(self):
+        return len(self.conds)
+
+
+def _cat_rows(cs):
+    c = cs[0]
+    if c is None:
+        return None
+    if torch.is_tensor(c):
+        return torch.cat(list(cs), dim=0)
+    if isinstance(c, dict):
+        return {k: _cat_rows([x[k] for x in cs]) for k in c}
+    if isinstance(c, (list, tuple)):
+        return type(c)(_cat_rows([x[i] for x in cs]) for i in range(len(c)))
+    return c
+
+
+def check_per_prompt(cond, plan, what="windows="):
+    """A row plan wants a PerPrompt of K = max(row_prompt) + 1 conditionings, every other plan (or none) anything else."""
+    rows = plan is not None and has_rows(plan)
+    if isinstance(cond, PerPrompt) != rows:
+        raise ValueError(f"{what}: a row plan (windows.row_plan) and a PerPrompt conditioning go together: got "
+                         f"{'a row plan' if rows else 'no row plan'} with {type(cond).__name__}")
+    if rows and len(cond) != max(plan.row_prompt) + 1:
+        raise ValueError(f"{what}: the row plan has {max(plan.row_prompt) + 1} prompts, the PerPrompt conditioning {len(cond)}")
+
+
+def rows_cond(per_prompt, plan):
+    """The conditioning of a row plan's UNet pass, row-major like ops.window_gather's rows: rows r*b + i, i in [0, b), are prompt
+    plan.row_prompt[r]'s conditioning (its b samples).  Tensors inside lists, tuples and dicts, None passing through."""
+    check_per_prompt(per_prompt, plan, "rows_cond")
+    return _cat_rows([per_prompt.conds[k] for k in plan.row_prompt])
 
 
 def keep_mask(T, intervals):
@@ -172,11 +334,11 @@ def with_source(plan, x0, mask):
 
 
 def device_weights(plan, device):
-    """plan.wn on `device`, uploaded once per plan and device."""
+    """plan.wn — a row plan's plan.wr — on `device`, uploaded once per plan and device."""
     cache = plan.__dict__.setdefault("_wn_dev", {})
     key = str(device)
     if key not in cache:
-        cache[key] = plan.wn.to(device).contiguous()
+        cache[key] = (plan.wr if has_rows(plan) else plan.wn).to(device).contiguous()
     return cache[key]
 
 

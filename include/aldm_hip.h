@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 /* ---- library / error ------------------------------------------------------------------ */
-int aldm_version(void);              /* ABI version (21), bumped on any struct / entry change */
+int aldm_version(void);              /* ABI version (22), bumped on any struct / entry change */
 const char* aldm_last_error(void);   /* message of the last failing call on this thread     */
 
 /* ---- activations usable as prologue (applied to the gathered input) or epilogue -------- */
@@ -641,6 +641,35 @@ int aldm_window_merge_ring(const float* win, const float* wn, float* out, aldm_w
 int aldm_window_blend_gather_ring(float* x, const float* x0, const float* qnoise, const float* mask, const float* blend_coef,
                                   const int* step_idx, int q_rows, int coef_rows, float* win, aldm_window_starts starts, int B,
                                   int W, int C, int T, int Tw, int F, void* stream);
+/* Prompt timelines, ABI v22: a ROW is one window under one prompt, so several rows may share a start.  The row starts
+ * travel by value like the window starts; 64 of them (a two-minute clip with a scene every 10 s takes 35).  The three entries below
+ * are siblings of aldm_window_gather, aldm_window_merge and aldm_window_blend_gather; those are unchanged and keep refusing repeated
+ * starts.  Host checks before every launch: 1 <= n <= ALDM_MAX_ROWS, s[0] == 0, s non-decreasing, every increase <= Tw (every
+ * frame has a row), s[n-1] == T - Tw, and the shape, overlap and pointer checks of the siblings.  Linear plans only.             */
+#define ALDM_MAX_ROWS 64
+typedef struct aldm_window_rows {
+    int n;
+    int s[ALDM_MAX_ROWS];
+} aldm_window_rows;
+/* win[(r*B + b), c, p, f] = x[b, c, s_r + p, f]: x [B, C, T, F] -> win [n*B, C, Tw, F], row-major; a bit-exact copy (rows that
+ * share a start are equal copies).  win must not overlap x.                                                                      */
+int aldm_window_gather_rows(const float* x, float* win, aldm_window_rows rows, int B, int C, int T, int Tw, int F, void* stream);
+/* The weighted overlap-add of row-wise tensors: win [H, n*B, C, Tw, F], wr [n, Tw] (per-row, per-frame weights: taper times prompt
+ * weight, normalised over the rows of a frame) -> out [H, B, C, T, F]; H = 1 | 2.
+ *   out[h, b, c, t, f] = sum over the rows r with s_r <= t < s_r + Tw AND wr[r, t - s_r] != 0, in ascending r, of
+ *                        wr[r, t - s_r] * win[h, r*B + b, c, t - s_r, f]
+ * in fp32: the first kept term a plain multiply, every later one one fmaf; a frame where every covering row has weight 0 (no plan
+ * of windows.row_plan has one) is written as 0.  A row of weight exactly 0 at a frame is SKIPPED there and its win element is not
+ * loaded: a prompt contributes nothing outside its region, not even 0 * NaN; a frame under one row of weight 1 reproduces its
+ * input bit for bit.  Gather form, no atomics.  out must overlap neither win nor wr.                                             */
+int aldm_window_merge_rows(const float* win, const float* wr, float* out, aldm_window_rows rows, int H, int B, int C, int T, int Tw,
+                           int F, void* stream);
+/* aldm_window_blend_gather over rows: in place x = (sa*x0 + so*qn)*m + (1 - m)*x with the sibling's expression, operation order and
+ * step-counter row selection, then win[(r*B + b), c, t - s_r, f] = x for every row r that covers t.  Every win element has exactly
+ * one writer.  Bitwise aldm_inpaint_blend followed by aldm_window_gather_rows.                                                   */
+int aldm_window_blend_gather_rows(float* x, const float* x0, const float* qnoise, const float* mask, const float* blend_coef,
+                                  const int* step_idx, int q_rows, int coef_rows, float* win, aldm_window_rows rows, int B, int C,
+                                  int T, int Tw, int F, void* stream);
 /* generic y = alpha*a + beta*b (b may be NULL) */
 int aldm_axpby(const float* a, const float* b, float* y, float alpha, float beta, int64_t n,
                void* stream);
