@@ -604,6 +604,44 @@ __global__ void inpaint_blend_kernel(const float* __restrict__ x0, const float* 
     }
 }
 
+// the forward jump of resampled inpainting (RePaint, Lugmayr et al. 2022, section 4.2), in place on the whole latent, between two
+// replays of the step graph:  x = c0*x + c1*noise_tab[s],  s = *step_idx (row 0 without a counter), {c0, c1} = coef_tab[s][0..1] =
+// {sqrt(rho), sqrt(1 - rho)}, rho = abar(k') / abar(k): q(x_k' | x_k) over the whole jump in one launch.  Two rounded products and
+// one rounded sum, in that order.  The counter is trusted as in ddim_step_indexed_kernel: step_advance_kernel saturates it at the
+// tables' last row.
+__global__ void renoise_indexed_kernel(float* __restrict__ x, const float* __restrict__ noise_tab, const float* __restrict__ coef_tab,
+                                       const int* __restrict__ step_idx, int64_t n, int coef_ld) {
+    const int s = step_idx ? *step_idx : 0;
+    const float c0 = coef_tab[(int64_t)s * coef_ld], c1 = coef_tab[(int64_t)s * coef_ld + 1];
+    const float* noise = noise_tab + (int64_t)s * n;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float a = c0 * x[i];
+        const float b = c1 * noise[i];
+        x[i] = a + b;
+    }
+}
+
+// the same with 16 bytes per lane and access: n4 = n / 4 for n % 4 == 0 and 16-byte aligned x and noise_tab (so is every row then)
+__global__ void renoise_indexed_vec4_kernel(float* __restrict__ x, const float* __restrict__ noise_tab,
+                                            const float* __restrict__ coef_tab, const int* __restrict__ step_idx, int64_t n4,
+                                            int coef_ld) {
+    const int s = step_idx ? *step_idx : 0;
+    const float c0 = coef_tab[(int64_t)s * coef_ld], c1 = coef_tab[(int64_t)s * coef_ld + 1];
+    f32x4* xq = reinterpret_cast<f32x4*>(x);
+    const f32x4* nq = reinterpret_cast<const f32x4*>(noise_tab) + (int64_t)s * n4;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+        f32x4 xv = xq[i];
+        const f32x4 nv = nq[i];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float a = c0 * xv[k];
+            const float b = c1 * nv[k];
+            xv[k] = a + b;
+        }
+        xq[i] = xv;
+    }
+}
+
 // VAE posterior sample fused with the forward diffusion to the sampler's first noise level (audio-to-audio, SDEdit):
 //   lv = clamp(logvar, -30, 20); std = exp(0.5 lv); z = scale*(mean + std*n_post); x_t[r] = sa*z[r % B0] + so*n_enc[r]
 // coef = {scale, sa = sqrt(abar), so = sqrt(1 - abar)}.  One thread per (source sample, pixel): adjacent threads take adjacent
@@ -670,6 +708,25 @@ extern "C" int aldm_inpaint_blend(const float* x0, const float* qnoise, const fl
     hipLaunchKernelGGL(inpaint_blend_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, x0,
                        qnoise, mask, coef, x, n);
     ALDM_LAUNCH_CHECK("aldm_inpaint_blend");
+    return 0;
+}
+
+extern "C" int aldm_renoise_indexed(float* x, const float* noise_tab, const float* coef_tab, const int* step_idx, int64_t n,
+                                    int coef_ld, void* stream) {
+    ALDM_CHECK(x && noise_tab && coef_tab, "aldm_renoise_indexed: null pointer");
+    ALDM_CHECK(n > 0 && coef_ld >= 2, "aldm_renoise_indexed: bad args (n=%lld, coef_ld=%d: rows of >= 2 floats)", (long long)n,
+               coef_ld);
+    // the table's row count does not cross this ABI: x is checked against the first row here, against the whole table by the
+    // host wrapper, which knows the rows
+    ALDM_CHECK(x + n <= noise_tab || noise_tab + n <= x, "aldm_renoise_indexed: x overlaps noise_tab");
+    const bool vec = n % 4 == 0 && (((uintptr_t)x | (uintptr_t)noise_tab) & 15) == 0;
+    if (vec)
+        hipLaunchKernelGGL(renoise_indexed_vec4_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, x, noise_tab,
+                           coef_tab, step_idx, n / 4, coef_ld);
+    else
+        hipLaunchKernelGGL(renoise_indexed_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, x, noise_tab, coef_tab,
+                           step_idx, n, coef_ld);
+    ALDM_LAUNCH_CHECK("aldm_renoise_indexed");
     return 0;
 }
 

@@ -26,9 +26,9 @@ import torch
 
 from . import ops
 # the samplers' shared core; every name below lived in this module before sampling.py existed and is still exported from here
-from .sampling import (GraphStepper, SamplerBase, _NoiseFeed, check_guidance_rescale, check_t_start,  # noqa: F401
+from .sampling import (GraphStepper, SamplerBase, _NoiseFeed, check_guidance_rescale, check_resample, check_t_start,  # noqa: F401
                        ddim_step_rows, drop_graph_entries, guidance_table, host_drawer, log_step, make_ddim_sampling_parameters,
-                       make_ddim_timesteps)
+                       make_ddim_timesteps, renoise_coef, resample_visits)
 
 
 
@@ -80,11 +80,14 @@ class DDIMSampler(SamplerBase):
                img_callback=None, quantize_x0=False, eta=0.0, mask=None, x0=None, temperature=1.0,
                noise_dropout=0.0, score_corrector=None, corrector_kwargs=None, verbose=True, x_T=None,
                log_every_t=100, unconditional_guidance_scale=1.0, unconditional_conditioning=None,
-               dynamic_threshold=None, ucg_schedule=None, guidance_rescale=0.0, t_start=None, windows=None, **kwargs):
+               dynamic_threshold=None, ucg_schedule=None, guidance_rescale=0.0, t_start=None, windows=None, resample=None,
+               **kwargs):
         """ddim.py:94-163, plus `guidance_rescale` (phi of Lin et al. 2023; 0: off — the reference's step), `t_start` (None: the
-        whole schedule; k: its first k entries, indices k-1 ... 0, from x_T — see check_t_start) and `windows` (None, or a
-        windows.window_plan over the long latent `shape`: windowed diffusion, see SamplerBase.plan_run)"""
+        whole schedule; k: its first k entries, indices k-1 ... 0, from x_T — see check_t_start), `windows` (None, or a
+        windows.window_plan over the long latent `shape`: windowed diffusion, see SamplerBase.plan_run) and `resample` (None, or
+        RePaint's pair (n, jump): resampled inpainting, see ddim_sampling)"""
         guidance_rescale = check_guidance_rescale(guidance_rescale)
+        self._refuse_resample(resample, temperature, mask, x0, windows)
         if quantize_x0 or score_corrector is not None or dynamic_threshold is not None \
                 or noise_dropout != 0.0 or ucg_schedule is not None:
             raise NotImplementedError("DDIMSampler(HIP): option not used by the AudioLDM2 pipeline")
@@ -97,7 +100,20 @@ class DDIMSampler(SamplerBase):
                                   log_every_t=log_every_t,
                                   unconditional_guidance_scale=unconditional_guidance_scale,
                                   unconditional_conditioning=unconditional_conditioning, guidance_rescale=guidance_rescale,
-                                  t_start=t_start, windows=windows)
+                                  t_start=t_start, windows=windows, resample=resample)
+
+    @staticmethod
+    def _refuse_resample(resample, temperature, mask, x0, windows):
+        """What `resample=` cannot go with, refused before the schedule is cut (plan_run refuses the values against the cut
+        schedule, before the run's first draw)."""
+        if check_resample(resample) is None:
+            return
+        if temperature != 1.0:
+            raise ValueError(f"resample= needs temperature == 1.0, got {temperature!r}: the noise feed scales the step-noise row, "
+                             "and the forward jump's noise must be unit")
+        if mask is None and x0 is None and getattr(windows, "x0", None) is None:
+            raise ValueError("resample= needs something to harmonise with: a mask / x0, or a source on the window plan "
+                             "(windows.with_source)")
 
     # ------------------------------------------------------------------------------------------
     def _draw_noise(self, shape, steps, x_T, with_mask):
@@ -119,12 +135,23 @@ class DDIMSampler(SamplerBase):
                       log_every_t=100, temperature=1.0, noise_dropout=0.0, score_corrector=None,
                       corrector_kwargs=None, unconditional_guidance_scale=1.0,
                       unconditional_conditioning=None, dynamic_threshold=None, ucg_schedule=None, guidance_rescale=0.0,
-                      t_start=None, windows=None):
+                      t_start=None, windows=None, resample=None):
         """ddim.py:166-262; `t_start=k`: run exactly the schedule's first k entries (check_t_start); `windows`: a window plan
         over the long latent `shape` (SamplerBase.plan_run) — gather and merge become two nodes of the step graph; a plan
         with a source (windows.with_source) blends the source in inside the step: the gather node becomes ops.window_blend_gather,
-        which reads the feed's q-noise table with the graph's step counter — the host issues nothing new per step"""
+        which reads the feed's q-noise table with the graph's step counter — the host issues nothing new per step.
+
+        `resample=(n, jump)` (RePaint's jump_n_sample and jump_length, in sampler steps): resampled inpainting.  The
+        run is a sequence of V visits (sampling.resample_visits), every table has V rows in visit order and the device counter
+        counts visits.  A step visit is the step it is without the keyword — the same replayed graph, captured once; a renoise
+        visit k -> k - jump is two host-issued launches between two replays: ops.renoise_indexed on the whole latent (the known
+        region is blended back in by the next step visit) with the visit's step-noise row as its unit noise, then
+        ops.step_advance.  EVERY visit makes the feed's draws in the feed's order (q-noise row, step-noise row); a renoise
+        visit's q-noise row is drawn and not read.  Callbacks and `intermediates` see step visits only, with the step's loop
+        position i (the schedule index total_steps - 1 - i), so a position that is sampled n times is reported n times.  Needs
+        a mask / x0 or a source on the plan, and temperature == 1.0; (1, jump) is the run without the keyword."""
         guidance_rescale = check_guidance_rescale(guidance_rescale)
+        self._refuse_resample(resample, temperature, mask, x0, windows)
         if ddim_use_original_steps:
             # the reference's own p_sample_ddim reads `self.model.ddim_sigmas_for_original_num_steps` here (ddim.py:324-327), a
             # buffer it registered on the SAMPLER (ddim.py:84-91): with LatentDiffusion as the model this path raises
@@ -139,12 +166,16 @@ class DDIMSampler(SamplerBase):
         plan = self.plan_run(cond, shape, x_T, t_start, timesteps,
                              lambda n, cfg: guidance_table(self.ddim_coef[:n].flip(0), unconditional_guidance_scale, cfg,
                                                            guidance_rescale),
-                             unconditional_guidance_scale, unconditional_conditioning, guidance_rescale, mask, x0, windows)
+                             unconditional_guidance_scale, unconditional_conditioning, guidance_rescale, mask, x0, windows,
+                             resample)
         total_steps, use_cfg, rescale, img, prepared = plan.total_steps, plan.use_cfg, plan.rescale, plan.img, plan.prepared
         cond, unconditional_conditioning = plan.cond, plan.uncond   # tiled W times in a windowed run, else the arguments
         intermediates = {"x_inter": [img], "pred_x0": [img]}
         if total_steps == 0:
             return img, intermediates
+        # resampled inpainting: the tables' rows — and the counter — are per VISIT (plan_run); without it a visit is a step
+        visits = plan.visits
+        n_rows = total_steps if visits is None else len(visits)
 
         # The captured step graph, its static input buffers and the batched conditioning live on the UNet
         # module and are reused by the next sampling run of the same geometry (text_to_audio in a loop):
@@ -195,7 +226,7 @@ class DDIMSampler(SamplerBase):
             ent = {"x_cur": img.clone(), "pred_x0": torch.empty_like(img), "t_cur": plan.t_tab[0].clone(),
                    "step_idx": torch.zeros(1, device=dev, dtype=torch.int32), "coef_all": plan.coef.clone(),
                    "t_tab": plan.t_tab.clone(),
-                   "noise_all": torch.empty((total_steps,) + shape, device=dev, dtype=torch.float32), "prepared": prepared}
+                   "noise_all": torch.empty((n_rows,) + shape, device=dev, dtype=torch.float32), "prepared": prepared}
             if rescale:
                 ent["eps_g"] = torch.empty_like(img)   # the rescaled combined model output
             if plan.win is not None:
@@ -228,17 +259,26 @@ class DDIMSampler(SamplerBase):
         # (ADVICE r3 + r4: opt-OUT, not opt-in — a silent interleaving gives a different noise stream with no diagnostic;
         # INTEGRATION.md §5; ALDM_NOISE_THREAD=0 forces the unthreaded feed for every run).
         cb_rng = any(getattr(f, "uses_rng", True) for f in (callback, img_callback) if f is not None)
-        feed = _NoiseFeed(plan.draw, total_steps, shape, mask is not None or blend, temperature, dev, noise_buf=ent["noise_all"],
+        feed = _NoiseFeed(plan.draw, n_rows, shape, mask is not None or blend, temperature, dev, noise_buf=ent["noise_all"],
                           qnoise_buf=ent.get("qnoise_all"), **({"threaded": False, "chunk": 1} if cb_rng else {}))
         feed.produce_next()
         qn = feed.qnoise
         run_step = ent["run_step"]
         try:
-            for i in range(total_steps):
-                opens_chunk = feed.wait(i)  # current stream waits for the upload of step i's noise chunk
+            for v in range(n_rows):
+                opens_chunk = feed.wait(v)  # current stream waits for the upload of visit v's noise chunk
+                if visits is not None and visits[v][0] == "renoise":
+                    # the forward jump k -> k - jump on the whole latent, between two replays: the counter selects the visit's
+                    # (c0, c1) and its step-noise row, as it does for a step; the step graph is neither touched nor re-captured
+                    ops.renoise_indexed(x_cur, ent["noise_all"], ent["coef_all"], ent["step_idx"])
+                    ops.step_advance(ent["step_idx"], ent["t_tab"], ent["t_cur"])
+                    if opens_chunk and not cb_rng:
+                        feed.produce_next()
+                    continue
+                i = v if visits is None else visits[v][1]   # the loop position of this step
                 if mask is not None:
                     # img = q_sample(x0, ts)*mask + (1-mask)*img   (ddim.py:226-231, ddpm.py:430-436)
-                    ops.inpaint_blend(x_cur, plan.x0_d, qn[i], plan.mask_d, plan.blend_coef[i])
+                    ops.inpaint_blend(x_cur, plan.x0_d, qn[v], plan.mask_d, plan.blend_coef[v])
                 run_step()  # eager the first time, then one HIP-graph replay per step
                 if can_cache and ent.get("kv") is None:
                     # after the eager first step: the K/V projections of this run's contexts exist; the cache entry owns

@@ -91,6 +91,9 @@ class DPMSolverSampler(SamplerBase):
         """PLMSSampler.sample's parameter list; S is the grid parameter of make_ddim_timesteps.  `guidance_rescale` is read from
         **kwargs, as there, and becomes `self.guidance_rescale` for this run."""
         self.guidance_rescale = check_guidance_rescale(kwargs.pop("guidance_rescale", 0.0))
+        if kwargs.get("resample") is not None:
+            raise ValueError("DPMSolverSampler: resample= (resampled inpainting) is DDIM's: the multistep history does not survive a "
+                             "jump back to a higher noise level")
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
         # `t_start` (None or absent: the whole schedule; k: its first k entries, indices k-1 ... 0, from x_T) is read from **kwargs
         # like `guidance_rescale`, and becomes `self.t_start` for this run

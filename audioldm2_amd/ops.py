@@ -1654,6 +1654,29 @@ def inpaint_blend(x: torch.Tensor, x0: torch.Tensor, qnoise: torch.Tensor, mask:
     return x
 
 
+def renoise_indexed(x: torch.Tensor, noise_tab: torch.Tensor, coef_tab: torch.Tensor,
+                    step_idx: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The forward jump of resampled inpainting, in place on x (aldm_renoise_indexed; RePaint):
+    x = c0*x + c1*noise_tab[s] with {c0, c1} = coef_tab[s, 0:2] and s the int32 device counter `step_idx` (None: row 0).  noise_tab
+    [V, *x.shape] (or one row [*x.shape]) and coef_tab [V', >= 2] are a sampling run's own tables; the counter is then advanced by
+    step_advance.  x may share no byte with noise_tab.  The counter is not range-checked (step_advance saturates it): the tables
+    must hold the rows it can reach."""
+    for t, n in ((x, "x"), (noise_tab, "noise_tab"), (coef_tab, "coef_tab")):
+        _chk(t, "renoise." + n)
+    if x.numel() == 0 or tuple(noise_tab.shape) not in (tuple(x.shape), tuple(noise_tab.shape[:1]) + tuple(x.shape)):
+        raise RuntimeError(f"renoise.noise_tab: expected {tuple(x.shape)} or [V, {', '.join(str(d) for d in x.shape)}], got "
+                           f"{tuple(noise_tab.shape)}")
+    if coef_tab.dim() != 2 or coef_tab.shape[1] < 2:
+        raise RuntimeError(f"renoise.coef_tab: expected a [V, >= 2] table, got {tuple(coef_tab.shape)}")
+    if step_idx is not None and not (step_idx.dtype == torch.int32 and step_idx.is_cuda and step_idx.numel() == 1):
+        raise RuntimeError(f"renoise.step_idx: expected one int32 CUDA element, got {step_idx.dtype} {step_idx.device} "
+                           f"numel={step_idx.numel()}")
+    _no_overlap(x, "renoise.x", [(noise_tab, "noise_tab")])
+    _l.check(_l.load().aldm_renoise_indexed(x.data_ptr(), noise_tab.data_ptr(), coef_tab.data_ptr(), _p(step_idx), x.numel(),
+                                            coef_tab.shape[1], _stream()), "renoise_indexed")
+    return x
+
+
 def posterior_qsample(moments_cl: torch.Tensor, n_post: torch.Tensor, n_enc: torch.Tensor, coef: torch.Tensor,
                       z: Optional[torch.Tensor] = None, x_t: Optional[torch.Tensor] = None):
     """The VAE posterior sample and its forward diffusion in one launch (aldm_posterior_qsample): moments_cl [B0, h, w, 2C]

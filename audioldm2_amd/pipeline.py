@@ -411,14 +411,34 @@ def _unconditional_half(ld, neg_batch, n_gen, batch_size, unconditional_guidance
     return unconditional_conditioning
 
 
-def _sample_log_keywords(sampler, guidance_rescale, t_start=None):
+def _sample_log_keywords(sampler, guidance_rescale, t_start=None, resample=None):
     """sample_log's optional keywords, each absent at its default: without them the call is the reference's."""
     kw = {} if sampler is None else {"sampler": sampler}
     if guidance_rescale != 0.0:
         kw["guidance_rescale"] = guidance_rescale
     if t_start is not None:
         kw["t_start"] = t_start
+    if resample is not None:
+        kw["resample"] = resample
     return kw
+
+
+RESAMPLE_MULTISTEP = ("resample= (resampled inpainting) runs on the DDIM sampler only: the multistep history of PLMS and "
+                      "DPM-Solver++(2M) does not survive a jump back to a higher noise level")
+
+
+def check_resample_job(resample, ddim_steps, sampler, use_plms, ld):
+    """The `resample=(n, jump)` keyword of the jobs that keep a source (generate_batch_masked, generate_batch_long_from_audio,
+    extend_audio), host only, before anything is drawn: None, or RePaint's pair checked against the sampler and the `ddim_steps`
+    schedule's length (sampling.resample_visits; `ld.num_timesteps` is read only when the keyword is set).  -> None or (n, jump)."""
+    from .sampling import check_resample, make_ddim_timesteps
+    if check_resample(resample) is None:
+        return None
+    if use_plms or sampler is not None:
+        raise ValueError(RESAMPLE_MULTISTEP)
+    if ddim_steps is None:
+        raise ValueError("resample= needs ddim_steps: the ancestral sampler has no jump schedule")
+    return check_resample(resample, len(make_ddim_timesteps("uniform", int(ddim_steps), int(ld.num_timesteps), verbose=False)))
 
 
 def _waveform_of(ld, samples, batch, text, n_gen, n_prompts, decision_shard=None):
@@ -705,6 +725,20 @@ class LatentDiffusion(nn.Module):
             raise ValueError("windows needs ddim_steps: the ancestral sampler has no windowed form")
         elif windows.Tw != self.latent_t_size:
             raise ValueError(f"windows: the plan's window is {windows.Tw} frames, the model's latent_t_size is {self.latent_t_size}")
+        # `resample` (a keyword of **kwargs: RePaint's pair (n, jump), resampled inpainting) goes to the DDIM sampler
+        # only, and needs a region to keep: a mask / x0, or a source on the window plan
+        if kwargs.get("resample", None) is None:
+            kwargs.pop("resample", None)   # absent: today's call, unchanged
+        else:
+            from .sampling import check_resample
+            check_resample(kwargs["resample"])
+            if use_plms or sampler_name is not None:
+                raise ValueError(RESAMPLE_MULTISTEP)
+            if not ddim:
+                raise ValueError("resample= needs ddim_steps: the ancestral sampler has no jump schedule")
+            if mask is None and kwargs.get("x0", None) is None and getattr(windows, "x0", None) is None:
+                raise ValueError("resample= needs something to harmonise with: a mask / x0, or a source on the window plan "
+                                 "(windows.with_source)")
         if mask is not None:
             shape = (self.channels, mask.size()[-2], mask.size()[-1])
         elif windows is not None:
@@ -990,10 +1024,13 @@ class LatentDiffusion(nn.Module):
                               use_plms=False, time_mask_ratio_start_and_end=(0.25, 0.75),
                               freq_mask_ratio_start_and_end=(0.75, 1.0), **kwargs):
         """ddpm.py:1573-1676 (inpainting / super-resolution): VAE-encode the given mel -> x0, keep the
-        unmasked latent region (DDIM blends q_sample(x0, t) back in every step), regenerate the rest."""
+        unmasked latent region (DDIM blends q_sample(x0, t) back in every step), regenerate the rest.
+        `resample=(n, jump)` (a keyword of **kwargs like `sampler`): resampled inpainting — RePaint's jumps back to a
+        higher noise level, so the generated region is re-made in the presence of the kept one; DDIM only, refused before any draw."""
         assert x_T is None
         sampler = resolve_sampler(kwargs.get("sampler", None), use_plms)
         neg_batch, guidance_rescale = _guidance_kwargs(kwargs, unconditional_guidance_scale, batch, ddim_steps)
+        resample = check_resample_job(kwargs.get("resample", None), ddim_steps, sampler, use_plms, self)
         if use_plms:
             assert ddim_steps is not None
         self._check_candidates(n_gen, batch.get("text"))
@@ -1018,7 +1055,8 @@ class LatentDiffusion(nn.Module):
         samples, _ = self.sample_log(cond=c, batch_size=batch_size, x_T=x_T, ddim=use_ddim, ddim_steps=ddim_steps,
                                      eta=ddim_eta, unconditional_guidance_scale=unconditional_guidance_scale,
                                      unconditional_conditioning=unconditional_conditioning, use_plms=use_plms,
-                                     mask=mask, x0=torch.cat([z] * n_gen), **_sample_log_keywords(sampler, guidance_rescale))
+                                     mask=mask, x0=torch.cat([z] * n_gen),
+                                     **_sample_log_keywords(sampler, guidance_rescale, resample=resample))
         return _waveform_of(self, samples, batch, text, n_gen, B0)
 
 
@@ -1217,7 +1255,8 @@ class LatentDiffusion(nn.Module):
     @torch.no_grad()
     def generate_batch_long_from_audio(self, batch, latent_t_size, keep, hop=None, ddim_steps=200, ddim_eta=1.0,
                                        unconditional_guidance_scale=1.0, use_plms=False, sampler=None, negative_prompt=None,
-                                       guidance_rescale=0.0, n_gen=1, shard=None, loop=False, boundaries=None, transition=0.0):
+                                       guidance_rescale=0.0, n_gen=1, shard=None, loop=False, boundaries=None, transition=0.0,
+                                       resample=None):
         """Continuation and inpainting of long clips: generate_batch_long around a source.  `batch["log_mel_spec"]`
         is the long mel [B0, latent_t_size*f, F_mel] of the source; `keep` lists the half-open latent-frame intervals [a, b) to
         keep (windows.keep_mask); everything else is generated under the prompt.  The source is encoded window by window
@@ -1237,14 +1276,22 @@ class LatentDiffusion(nn.Module):
         mel), `boundaries`, `transition`; the source rides on the row plan, the blend writes every covering row
         (aldm_window_blend_gather_rows).  Not together with loop=True.
 
+        `resample=(n, jump)`: resampled inpainting, RePaint's jump_n_sample and jump_length in sampler steps.  After
+        every `jump` steps the LONG latent is diffused forward again by `jump` noise levels (one launch, aldm_renoise_indexed) and
+        those levels are denoised once more, n - 1 times per jump point, the known region blended back in by the next step's fused
+        blend-and-gather — on a linear, a ring and a row plan alike.  DDIM only; n = 1 is the job without the keyword.  The job
+        runs V_step / ddim_steps times as many UNet steps and holds two noise tables of V rows at the long latent's size.
+
         Refused before any draw or GPU work: ddim_steps=None, n_gen != 1, shard=, bad lengths or hops (long_form_plans), a bad
-        `keep`, a mel whose length is not latent_t_size*f, a bad timeline (generate_batch_long).
+        `keep`, a mel whose length is not latent_t_size*f, a bad timeline (generate_batch_long), a bad `resample` (a malformed pair,
+        n < 1, jump outside [1, steps - 1], together with use_plms=True or sampler="dpmpp_2m").
 
         Host-generator order (RNG contract R): (R1) randn(B0, C, latent_t_size, F) at the LONG shape, the
         posterior noise, really used; (R1b) the rand(1) of _cfg_dropout_draw on every call but an object's first; the
         conditioners' draws (twice with a negative prompt); randn(B0, C, latent_t_size, F), the long x_T; per step at the long
         shape: DDIM the q-noise then the step noise, PLMS the q-noise then its own draws, DPM-Solver++ the q-noise only.  A timeline:
-        the conditioners' draws once per prompt in timeline order, then the negative prompt's."""
+        the conditioners' draws once per prompt in timeline order, then the negative prompt's.  With `resample`, "per step" reads
+        "per visit": the same two draws for each of the V visits, a renoise visit's q-noise drawn and not read."""
         from .windows import keep_mask, with_source
         batches, batch = _timeline_batches(batch, boundaries, loop, "generate_batch_long_from_audio")
         if shard is not None:
@@ -1258,6 +1305,7 @@ class LatentDiffusion(nn.Module):
         kw = {} if negative_prompt is None else {"negative_prompt": negative_prompt}
         neg_batch, guidance_rescale = _guidance_kwargs(dict(kw, guidance_rescale=guidance_rescale), unconditional_guidance_scale,
                                                        batch, ddim_steps)
+        resample = check_resample_job(resample, ddim_steps, sampler, use_plms, self)
         plan, mel_plan = self.long_form_plans(latent_t_size, hop)
         ring_plans = self.long_form_plans(latent_t_size, hop, ring=True) if loop else None   # refuses a bad ring before any draw
         mask_t = keep_mask(plan.T, keep)
@@ -1280,7 +1328,8 @@ class LatentDiffusion(nn.Module):
         samples, _ = self.sample_log(cond=c, batch_size=B0, x_T=None, ddim=True, ddim_steps=ddim_steps, eta=ddim_eta,
                                      unconditional_guidance_scale=unconditional_guidance_scale,
                                      unconditional_conditioning=unconditional_conditioning, use_plms=use_plms,
-                                     windows=with_source(run_plan, z, mask_t), **_sample_log_keywords(sampler, guidance_rescale))
+                                     windows=with_source(run_plan, z, mask_t),
+                                     **_sample_log_keywords(sampler, guidance_rescale, resample=resample))
         return self._long_tail(samples, plan, mel_plan, batch)
 
 
@@ -1620,7 +1669,7 @@ def keep_frames(keep, per_second, latent_t):
 
 def extend_audio(latent_diffusion, text, original_audio_file_path, duration, keep=None, overlap=2.5, transcription="", seed=42,
                  ddim_steps=200, guidance_scale=3.5, sampler=None, negative_prompt=None, guidance_rescale=0.0, loop=False,
-                 timeline=None, transition=0.0):
+                 timeline=None, transition=0.0, resample=None):
     """Continue or inpaint a long clip: a clip of `duration` seconds — longer than the model's trained length — that keeps parts
     of the recording `original_audio_file_path` (a path, or a 1-D float waveform at 16 kHz; zero-padded or cut to `duration`) and
     generates the rest under the prompt `text` by windowed diffusion (LatentDiffusion.generate_batch_long_from_audio).  `keep`
@@ -1634,12 +1683,20 @@ def extend_audio(latent_diffusion, text, original_audio_file_path, duration, kee
     `loop=True`: the generated part runs back into the source's beginning, so the whole clip loops ("make my 8 seconds loop by
     generating a 4-second bridge": duration=12, the default keep); `overlap` must then be positive.
     `timeline` / `transition`: a prompt timeline for the generated part, as in text_to_audio_long (`text` must then be None).
+    `resample=(n, jump)`: resampled inpainting (RePaint's jump_n_sample and jump_length, in sampler steps) — after
+    every `jump` steps the latent is diffused forward again by `jump` noise levels and those are denoised once more, n - 1 times per
+    jump point, so the generated part is re-made in the presence of the kept one; the paper's setting is (10, 10) at 250 steps.
+    DDIM only; the job runs (steps + (n - 1) * jump * points) / steps times as long.  With `keep=[...]` this is resampled inpainting
+    at any duration from the trained length up; the reference-API route at the trained length is
+    LatentDiffusion.generate_batch_masked(..., resample=...).
     Returns np.float32 [1, 1, samples]."""
     from .stft import TacotronSTFT
     from .windows import keep_mask
     sampler_kw = _sampler_kwargs(sampler, negative_prompt, guidance_rescale)
     if ddim_steps is None:
         raise ValueError("extend_audio needs ddim_steps: the ancestral sampler has no windowed form")
+    if check_resample_job(resample, ddim_steps, sampler, False, latent_diffusion) is not None:
+        sampler_kw["resample"] = resample
     from .sampling import check_guidance_rescale
     check_guidance_rescale(guidance_rescale)
     per_second = float(latent_diffusion.latent_t_per_second)

@@ -64,6 +64,9 @@ class PLMSSampler(SamplerBase):
         """plms.py:91-154; `guidance_rescale` (phi of Lin et al. 2023; 0 or absent: off — the reference's step) is read from
         **kwargs, so the signature stays the reference's, and becomes `self.guidance_rescale` for this run"""
         self.guidance_rescale = check_guidance_rescale(kwargs.pop("guidance_rescale", 0.0))
+        if kwargs.get("resample") is not None:
+            raise ValueError("PLMSSampler: resample= (resampled inpainting) is DDIM's: the multistep history does not survive a jump "
+                             "back to a higher noise level")
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
         # `t_start` (None or absent: the whole schedule; k: its first k entries, indices k-1 ... 0, from x_T) is read from **kwargs
         # like `guidance_rescale`, and becomes `self.t_start` for this run

@@ -9,7 +9,9 @@ run that is the same whichever update rule runs.
     a sampler's [S, 8] table from its rows;
   * GraphStepper / drop_graph_entries: a fixed launch sequence run eagerly once, captured into a HIP graph, replayed;
   * host_drawer / _NoiseFeed: the host generator's draws in the reference's order (RNG contract, SURVEY.md §8 row R);
-  * check_guidance_rescale / check_t_start: the two per-run options every sampler takes; log_step: the tail of every step.
+  * check_guidance_rescale / check_t_start: the two per-run options every sampler takes; log_step: the tail of every step;
+  * resample_visits / renoise_coef / check_resample: the visit schedule and the forward-jump coefficients of resampled inpainting
+    (RePaint's jumps, `resample=(n, jump)`), which plan_run turns into per-visit tables for DDIM's loop.
 
 What differs between the samplers stays in their modules: DDIM's graph cache on the UNet and its threaded noise feed, PLMS's eager
 Euler step 0 and its discarded `noise_like` draws, DPM-Solver++'s table per sub-range.  ddim.py re-exports every name that lived
@@ -311,6 +313,83 @@ def check_t_start(t_start, timesteps, schedule_len):
     return int(t_start)
 
 
+def _integer(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+
+
+def _resample_pair(n, jump):
+    """What can be refused of RePaint's (n, jump) before the run's step count is known."""
+    if not _integer(n) or not _integer(jump):
+        raise ValueError(f"resample=(n, jump) must be a pair of integers, got ({n!r}, {jump!r})")
+    if n < 1:
+        raise ValueError(f"resample: n (how often each stretch is sampled) must be >= 1, got {n}")
+    if jump < 1:
+        raise ValueError(f"resample: jump must lie in [1, steps - 1], got {jump}")
+
+
+def resample_visits(S, n, jump):
+    """Pure host function: the visit schedule of resampled inpainting (RePaint, Lugmayr et al. 2022, section 4.2) over
+    a run of S sampler steps.  n is RePaint's jump_n_sample — how often every stretch is sampled, 1: off — and jump its jump_length,
+    in sampler steps.  Position k in [0, S] counts the net steps completed; loop step i takes the latent from position i to i + 1
+    with schedule index S - 1 - i.  A jump point is a position k with (S - k) % jump == 0 and k > jump (the published schedule's
+    points: 0, jump, 2*jump, ... steps remaining, strictly below S - jump).  When loop step k - 1 ends on a jump point used fewer
+    than n - 1 times, the latent is diffused forward again to position k - jump and the run goes on from loop step k - jump: jump
+    points do not nest, and each is used exactly n - 1 times.
+    -> a tuple of visits, each ("step", i) or ("renoise", k, k - jump).  ValueError: n or jump no integer (a bool is none), n < 1,
+    jump outside [1, S - 1] — with jump >= S there is no jump point and the keyword would be silently ignored."""
+    if not _integer(S) or S < 1:
+        raise ValueError(f"resample: the run must have a positive integer number of steps, got {S!r}")
+    _resample_pair(n, jump)
+    if jump > S - 1:
+        raise ValueError(f"resample: jump must lie in [1, {S - 1}] for a run of {S} steps, got {jump}: with jump >= the number of "
+                         "steps there is no jump point and the keyword would be ignored")
+    S, n, jump = int(S), int(n), int(jump)
+    used, visits, i = {}, [], 0
+    while i < S:
+        visits.append(("step", i))
+        k = i + 1
+        if (S - k) % jump == 0 and k > jump and used.get(k, 0) < n - 1:
+            used[k] = used.get(k, 0) + 1
+            visits.append(("renoise", k, k - jump))
+            k -= jump
+        i = k
+    return tuple(visits)
+
+
+def renoise_coef(ddim_alphas, ddim_alphas_prev, S, k, k_to):
+    """Pure host function: (c0, c1) of the forward jump from position k down to k_to < k of a run of S steps (resample_visits),
+    x <- c0*x + c1*eps: q(x_k_to | x_k) of the DDPM forward process over the whole jump.  The noise level at position p is
+    abar(p) = ddim_alphas[S - 1 - p] for p < S — what loop step p takes its input to be at — and abar(S) = ddim_alphas_prev[0], the
+    level the last step leaves; rho = abar(k_to) / abar(k) < 1, c0 = sqrt(rho), c1 = sqrt(1 - rho).  Evaluated in fp64 from the
+    schedule as given and returned as Python floats (the caller rounds them to fp32 once)."""
+    if not 0 <= k_to < k <= S:
+        raise ValueError(f"renoise_coef: positions must satisfy 0 <= k_to < k <= S, got k={k!r}, k_to={k_to!r}, S={S!r}")
+    a = np.asarray(ddim_alphas.detach().cpu().numpy() if torch.is_tensor(ddim_alphas) else ddim_alphas, dtype=np.float64)
+    ap = np.asarray(ddim_alphas_prev.detach().cpu().numpy() if torch.is_tensor(ddim_alphas_prev) else ddim_alphas_prev,
+                    dtype=np.float64)
+
+    def abar(p):
+        return float(a[S - 1 - p]) if p < S else float(ap[0])
+    rho = abar(k_to) / abar(k)
+    if not 0.0 < rho < 1.0:
+        raise ValueError(f"renoise_coef: abar({k_to}) / abar({k}) = {rho!r} is not in (0, 1): the schedule does not descend")
+    return float(np.sqrt(rho)), float(np.sqrt(1.0 - rho))
+
+
+def check_resample(resample, S=None):
+    """The `resample=` keyword of DDIMSampler.sample / ddim_sampling and the pipeline's source-keeping jobs: None, or RePaint's pair
+    (n, jump) — see resample_visits, which refuses the values once the run's step count S is known.  -> None, or (n, jump)."""
+    if resample is None:
+        return None
+    if isinstance(resample, (str, bytes)) or not hasattr(resample, "__len__") or len(resample) != 2:
+        raise ValueError(f"resample must be None or a pair (n, jump) of integers, got {resample!r}")
+    n, jump = resample
+    if S is None:
+        _resample_pair(n, jump)
+    else:
+        resample_visits(S, n, jump)
+    return int(n), int(jump)
+
 
 def ddim_step_rows(sigmas, alphas, alphas_prev, sqrt_one_minus_alphas):
     """Pure host function: the [S, 5] fp32 rows {sqrt(1 - a_t), sqrt(a_t), sqrt(1 - a_prev - sigma_t^2), sqrt(a_prev), sigma_t} of
@@ -429,7 +508,7 @@ class SamplerBase(object):
         return torch.stack([self.model.apply_model(x, tl, uncond), self.model.apply_model(x, tl, cond)]).contiguous()
 
     def plan_run(self, cond, shape, x_T, t_start, timesteps, table, unconditional_guidance_scale, unconditional_conditioning,
-                 guidance_rescale, mask, x0, windows=None):
+                 guidance_rescale, mask, x0, windows=None, resample=None):
         """Everything a sampling loop needs before its first step, as one object.  `table(total_steps, use_cfg)` is the sampler's
         own [total_steps, 8] host coefficient table in loop order (i = 0 is the noisiest step, index = total_steps - 1).
 
@@ -448,6 +527,14 @@ class SamplerBase(object):
         check_t_start); `timesteps` keeps its first int(min(timesteps / S, 1) * S) - 1 entries (ddim.py:198-206).  `total_steps`
         may be 0 (`timesteps` <= one interval): the reference's loop then runs zero iterations and returns x_T, and nothing past
         `img` is built.
+
+        `resample` (None, or RePaint's pair (n, jump)): resampled inpainting.  The run becomes a sequence of V
+        visits (resample_visits over the cut schedule's `total_steps`), `p.visits`, and EVERY table gets V rows in visit order —
+        coef, t_tab, blend_coef, and (the sampler's) noise and q-noise tables — so the device-side counter that selects a step's
+        rows counts visits.  A step visit at loop position i has the rows position i has without the keyword; a renoise visit's
+        coefficient row is (c0, c1, 0, ...) of renoise_coef, its t_tab and blend_coef rows — not read — are the next step visit's.
+        Refused (ValueError) before the first draw: a malformed pair or values resample_visits refuses, and a run with nothing to
+        harmonise with (no mask / x0 and no source on the plan).  n == 1 is the plain run: p.visits is None, as without the keyword.
 
         RNG contract R: x_T is the host generator's first draw of the run, made only when x_T is not given; `draw` makes the
         loop's later ones.  A start latent that already lives on the device (audio-to-audio) stays there.  Host -> device copies,
@@ -478,7 +565,15 @@ class SamplerBase(object):
         total_steps = ts.shape[0]
         use_cfg = not (unconditional_conditioning is None or unconditional_guidance_scale == 1.0)
         p = SimpleNamespace(total_steps=total_steps, use_cfg=use_cfg, mask_d=None, x0_d=None, blend_coef=None, prepared=None,
-                            cond=cond, uncond=unconditional_conditioning, win=None)
+                            cond=cond, uncond=unconditional_conditioning, win=None, visits=None)
+        if resample is not None:
+            if mask is None and x0 is None and source is None:
+                raise ValueError("resample= needs something to harmonise with: a mask / x0, or a source on the window plan "
+                                 "(windows.with_source)")
+            if total_steps == 0:
+                raise ValueError("resample=: the cut schedule has no step to run")
+            if check_resample(resample, total_steps)[0] > 1:
+                p.visits = resample_visits(total_steps, *resample)
         p.time_range = np.flip(ts).copy()   # own storage, positive strides: from_numpy refuses the flipped view, even of one entry
         # guidance rescale: the combine and the per-sample rescale run in a launch of their own in front of the step kernel
         p.rescale = use_cfg and guidance_rescale > 0.0
@@ -486,8 +581,19 @@ class SamplerBase(object):
         p.img = (p.draw().to(dev) if x_T is None else x_T.detach().float().to(dev)).contiguous()
         if total_steps == 0:
             return p
-        p.coef = table(total_steps, use_cfg).to(dev)
+        coef = table(total_steps, use_cfg)
         tr = torch.from_numpy(p.time_range)
+        if p.visits is not None:
+            # one table row per VISIT: a step visit takes its loop position's row, a renoise visit the next step visit's (it reads
+            # neither its timestep nor its blend coefficients) — and its own (c0, c1, 0, ...) as the coefficient row
+            rows = torch.tensor([v[1] if v[0] == "step" else v[2] for v in p.visits], dtype=torch.long)
+            coef = coef[rows].clone()
+            for r, v in enumerate(p.visits):
+                if v[0] == "renoise":
+                    coef[r] = 0.0
+                    coef[r, 0], coef[r, 1] = renoise_coef(self.ddim_alphas, self.ddim_alphas_prev, total_steps, v[1], v[2])
+            tr = tr[rows]
+        p.coef = coef.to(dev)
         p.t_tab = tr.float()[:, None].repeat(1, (2 if use_cfg else 1) * W * shape[0]).to(dev).contiguous()
         if source is not None:
             mask, x0 = source

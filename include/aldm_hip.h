@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 /* ---- library / error ------------------------------------------------------------------ */
-int aldm_version(void);              /* ABI version (22), bumped on any struct / entry change */
+int aldm_version(void);              /* ABI version (23), bumped on any struct / entry change */
 const char* aldm_last_error(void);   /* message of the last failing call on this thread     */
 
 /* ---- activations usable as prologue (applied to the gathered input) or epilogue -------- */
@@ -576,6 +576,16 @@ int aldm_ddpm_step(const float* x, const float* eps, const float* noise, const f
  *   x = (sa*x0 + so*qnoise)*mask + (1 - mask)*x,  coef (device) = {sqrt(abar_t), sqrt(1 - abar_t)} */
 int aldm_inpaint_blend(const float* x0, const float* qnoise, const float* mask, const float* coef,
                        float* x, int64_t n, void* stream);
+/* The forward jump of resampled inpainting (RePaint, Lugmayr et al. 2022, section 4.2; ABI v23), in place on x:
+ *   s = step_idx ? *step_idx : 0;  x[i] = c0*x[i] + c1*noise_tab[s*n + i],  c0 = coef_tab[s*coef_ld], c1 = coef_tab[s*coef_ld + 1]
+ * with {c0, c1} = {sqrt(rho), sqrt(1 - rho)}, rho = abar(k') / abar(k) < 1: q(x_k' | x_k) of the forward process over the whole jump,
+ * one launch per jump.  fp32, two rounded products and one rounded sum in that order (no contraction): bitwise reproducible.  It reads
+ * the step graph's own counter, noise table and coefficient table (rows of coef_ld >= 2 floats) and is followed by
+ * aldm_step_advance; the step graph itself is untouched.  The counter is not range-checked, as in aldm_ddim_step_indexed:
+ * aldm_step_advance saturates it at the last row.  x may not overlap noise_tab (checked against its first row: the row count does
+ * not cross this ABI).  No atomics, nothing kept between launches.                                                              */
+int aldm_renoise_indexed(float* x, const float* noise_tab, const float* coef_tab, const int* step_idx, int64_t n, int coef_ld,
+                         void* stream);
 /* VAE posterior sample fused with the forward diffusion to the sampler's first noise level (audio-to-audio; ABI v16): one launch
  * from the encoder's channels-last moments (autoencoder.py:103-109, distributions.py:24-41, ddpm.py:793-802, ddim.py:434-449):
  *   moments_cl [B0, hw, 2C] channels-last: mean = channels 0..C-1, logvar = channels C..2C-1
