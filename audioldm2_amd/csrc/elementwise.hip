@@ -642,6 +642,40 @@ __global__ void renoise_indexed_vec4_kernel(float* __restrict__ x, const float* 
     }
 }
 
+// graded keep levels (differential diffusion, Levin & Fried 2023), in front of a step's blend:  mask = level > thr_tab[r] ? 1 : 0,
+// r = the counter clamped into [0, rows - 1] (row 0 without a counter) — the blend-gather kernels' conventions.  The blend then reads
+// a BINARY mask: a frame of level m is held on q_sample(source, t) while the step's threshold lies below m and is free afterwards.
+// The comparison is an ordered one, so a NaN level gives 0; the two values stored are the bit patterns of 0.0f and 1.0f.
+__device__ __forceinline__ float keep_threshold_row(const float* __restrict__ thr_tab, const int* __restrict__ step_idx, int rows) {
+    int r = step_idx ? *step_idx : 0;
+    r = r < 0 ? 0 : (r > rows - 1 ? rows - 1 : r);
+    return thr_tab[r];
+}
+
+__global__ void keep_threshold_indexed_kernel(const float* __restrict__ level, const float* __restrict__ thr_tab,
+                                              const int* __restrict__ step_idx, int rows, float* __restrict__ mask, int64_t n) {
+    const float thr = keep_threshold_row(thr_tab, step_idx, rows);
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        mask[i] = level[i] > thr ? 1.0f : 0.0f;
+}
+
+// the same with 16 bytes per lane and access: n4 = n / 4 for n % 4 == 0 and 16-byte aligned level and mask
+__global__ void keep_threshold_indexed_vec4_kernel(const float* __restrict__ level, const float* __restrict__ thr_tab,
+                                                   const int* __restrict__ step_idx, int rows, float* __restrict__ mask,
+                                                   int64_t n4) {
+    const float thr = keep_threshold_row(thr_tab, step_idx, rows);
+    const f32x4* lq = reinterpret_cast<const f32x4*>(level);
+    f32x4* mq = reinterpret_cast<f32x4*>(mask);
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+        const f32x4 lv = lq[i];
+        f32x4 mv;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            mv[k] = lv[k] > thr ? 1.0f : 0.0f;
+        mq[i] = mv;
+    }
+}
+
 // VAE posterior sample fused with the forward diffusion to the sampler's first noise level (audio-to-audio, SDEdit):
 //   lv = clamp(logvar, -30, 20); std = exp(0.5 lv); z = scale*(mean + std*n_post); x_t[r] = sa*z[r % B0] + so*n_enc[r]
 // coef = {scale, sa = sqrt(abar), so = sqrt(1 - abar)}.  One thread per (source sample, pixel): adjacent threads take adjacent
@@ -727,6 +761,24 @@ extern "C" int aldm_renoise_indexed(float* x, const float* noise_tab, const floa
         hipLaunchKernelGGL(renoise_indexed_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, x, noise_tab, coef_tab,
                            step_idx, n, coef_ld);
     ALDM_LAUNCH_CHECK("aldm_renoise_indexed");
+    return 0;
+}
+
+extern "C" int aldm_keep_threshold_indexed(const float* level, const float* thr_tab, const int* step_idx, int rows, float* mask,
+                                           int64_t n, void* stream) {
+    ALDM_CHECK(level && thr_tab && mask, "aldm_keep_threshold_indexed: null pointer");
+    ALDM_CHECK(n > 0 && rows > 0, "aldm_keep_threshold_indexed: bad args (n=%lld, rows=%d: both must be positive)", (long long)n,
+               rows);
+    // in place would destroy the levels, which every later step thresholds again
+    ALDM_CHECK(mask + n <= level || level + n <= mask, "aldm_keep_threshold_indexed: mask overlaps level");
+    const bool vec = n % 4 == 0 && (((uintptr_t)level | (uintptr_t)mask) & 15) == 0;
+    if (vec)
+        hipLaunchKernelGGL(keep_threshold_indexed_vec4_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, level,
+                           thr_tab, step_idx, rows, mask, n / 4);
+    else
+        hipLaunchKernelGGL(keep_threshold_indexed_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, level, thr_tab,
+                           step_idx, rows, mask, n);
+    ALDM_LAUNCH_CHECK("aldm_keep_threshold_indexed");
     return 0;
 }
 

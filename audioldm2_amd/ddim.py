@@ -81,11 +81,12 @@ class DDIMSampler(SamplerBase):
                noise_dropout=0.0, score_corrector=None, corrector_kwargs=None, verbose=True, x_T=None,
                log_every_t=100, unconditional_guidance_scale=1.0, unconditional_conditioning=None,
                dynamic_threshold=None, ucg_schedule=None, guidance_rescale=0.0, t_start=None, windows=None, resample=None,
-               **kwargs):
+               graded=False, **kwargs):
         """ddim.py:94-163, plus `guidance_rescale` (phi of Lin et al. 2023; 0: off — the reference's step), `t_start` (None: the
         whole schedule; k: its first k entries, indices k-1 ... 0, from x_T — see check_t_start), `windows` (None, or a
         windows.window_plan over the long latent `shape`: windowed diffusion, see SamplerBase.plan_run) and `resample` (None, or
-        RePaint's pair (n, jump): resampled inpainting, see ddim_sampling)"""
+        RePaint's pair (n, jump): resampled inpainting, see ddim_sampling) and `graded` (True: `mask` is a map of keep levels in
+        [0, 1], graded keep, see ddim_sampling)"""
         guidance_rescale = check_guidance_rescale(guidance_rescale)
         self._refuse_resample(resample, temperature, mask, x0, windows)
         if quantize_x0 or score_corrector is not None or dynamic_threshold is not None \
@@ -100,7 +101,7 @@ class DDIMSampler(SamplerBase):
                                   log_every_t=log_every_t,
                                   unconditional_guidance_scale=unconditional_guidance_scale,
                                   unconditional_conditioning=unconditional_conditioning, guidance_rescale=guidance_rescale,
-                                  t_start=t_start, windows=windows, resample=resample)
+                                  t_start=t_start, windows=windows, resample=resample, graded=graded)
 
     @staticmethod
     def _refuse_resample(resample, temperature, mask, x0, windows):
@@ -135,7 +136,7 @@ class DDIMSampler(SamplerBase):
                       log_every_t=100, temperature=1.0, noise_dropout=0.0, score_corrector=None,
                       corrector_kwargs=None, unconditional_guidance_scale=1.0,
                       unconditional_conditioning=None, dynamic_threshold=None, ucg_schedule=None, guidance_rescale=0.0,
-                      t_start=None, windows=None, resample=None):
+                      t_start=None, windows=None, resample=None, graded=False):
         """ddim.py:166-262; `t_start=k`: run exactly the schedule's first k entries (check_t_start); `windows`: a window plan
         over the long latent `shape` (SamplerBase.plan_run) — gather and merge become two nodes of the step graph; a plan
         with a source (windows.with_source) blends the source in inside the step: the gather node becomes ops.window_blend_gather,
@@ -149,7 +150,14 @@ class DDIMSampler(SamplerBase):
         ops.step_advance.  EVERY visit makes the feed's draws in the feed's order (q-noise row, step-noise row); a renoise
         visit's q-noise row is drawn and not read.  Callbacks and `intermediates` see step visits only, with the step's loop
         position i (the schedule index total_steps - 1 - i), so a position that is sampled n times is reported n times.  Needs
-        a mask / x0 or a source on the plan, and temperature == 1.0; (1, jump) is the run without the keyword."""
+        a mask / x0 or a source on the plan, and temperature == 1.0; (1, jump) is the run without the keyword.
+
+        `graded=True`: `mask` is a map of keep LEVELS in [0, 1] (differential diffusion; windows.keep_levels).  In
+        front of every blend one launch, ops.keep_threshold_indexed, rewrites the binary mask the blend reads from the levels and
+        the visit's threshold (sampling.keep_thresholds): a frame of level m is replaced by q_sample(x0, t) for its first
+        sampling.hold_steps(m, S) steps and is free afterwards.  A windowed run issues it inside the captured step (model_output),
+        the plain masked loop between the replays.  The draws and their order do not change.  Refused before any draw: no mask
+        or source, levels outside [0, 1] or not finite.  A source on the plan carries its own flag (windows.with_source)."""
         guidance_rescale = check_guidance_rescale(guidance_rescale)
         self._refuse_resample(resample, temperature, mask, x0, windows)
         if ddim_use_original_steps:
@@ -167,7 +175,7 @@ class DDIMSampler(SamplerBase):
                              lambda n, cfg: guidance_table(self.ddim_coef[:n].flip(0), unconditional_guidance_scale, cfg,
                                                            guidance_rescale),
                              unconditional_guidance_scale, unconditional_conditioning, guidance_rescale, mask, x0, windows,
-                             resample)
+                             resample, graded)
         total_steps, use_cfg, rescale, img, prepared = plan.total_steps, plan.use_cfg, plan.rescale, plan.img, plan.prepared
         cond, unconditional_conditioning = plan.cond, plan.uncond   # tiled W times in a windowed run, else the arguments
         intermediates = {"x_inter": [img], "pred_x0": [img]}
@@ -278,6 +286,8 @@ class DDIMSampler(SamplerBase):
                 i = v if visits is None else visits[v][1]   # the loop position of this step
                 if mask is not None:
                     # img = q_sample(x0, ts)*mask + (1-mask)*img   (ddim.py:226-231, ddpm.py:430-436)
+                    if plan.level_d is not None:   # graded keep levels: this visit's binary mask first
+                        ops.keep_threshold_indexed(plan.level_d, plan.keep_thr[v:v + 1], plan.mask_d)
                     ops.inpaint_blend(x_cur, plan.x0_d, qn[v], plan.mask_d, plan.blend_coef[v])
                 run_step()  # eager the first time, then one HIP-graph replay per step
                 if can_cache and ent.get("kv") is None:

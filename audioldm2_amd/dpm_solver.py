@@ -68,6 +68,7 @@ class DPMSolverSampler(SamplerBase):
         self.guidance_rescale = 0.0
         self.t_start = None   # the same way: `sample` sets it from its `t_start=` keyword (absent: None), `dpm_sampling` reads it
         self.windows = None   # the same way: a windows.window_plan over the long latent (`windows=`), or None
+        self.graded = False   # the same way: `mask` is a map of keep levels in [0, 1] (`graded=`)
 
     def make_schedule(self, ddim_num_steps, ddim_discretize="uniform", ddim_eta=0.0, verbose=True):
         """DDIM's timestep grid and abar tables at eta = 0 (host side), and the solver's coefficient table for the whole grid."""
@@ -99,6 +100,7 @@ class DPMSolverSampler(SamplerBase):
         # like `guidance_rescale`, and becomes `self.t_start` for this run
         self.t_start = check_t_start(kwargs.pop("t_start", None), kwargs.get("timesteps"), len(self.ddim_timesteps))
         self.windows = kwargs.pop("windows", None)   # the same way: windowed diffusion over the long `shape` (SamplerBase.plan_run)
+        self.graded = bool(kwargs.pop("graded", False))   # the same way: `mask` holds keep levels (SamplerBase.plan_run)
         C, H, W = shape
         size = (batch_size, C, H, W)
         return self.dpm_sampling(conditioning, size, callback=callback, img_callback=img_callback,
@@ -126,7 +128,8 @@ class DPMSolverSampler(SamplerBase):
         plan = self.plan_run(cond, shape, x_T, self.t_start, timesteps,
                              lambda n, cfg: guidance_table(self.dpm_coef if n == self.dpm_coef.shape[0] else self._table(n),
                                                            unconditional_guidance_scale, cfg, guidance_rescale),
-                             unconditional_guidance_scale, unconditional_conditioning, guidance_rescale, mask, x0, self.windows)
+                             unconditional_guidance_scale, unconditional_conditioning, guidance_rescale, mask, x0, self.windows,
+                             graded=self.graded)
         total_steps, use_cfg, rescale, draw, img = plan.total_steps, plan.use_cfg, plan.rescale, plan.draw, plan.img
         cond, unconditional_conditioning = plan.cond, plan.uncond   # tiled W times in a windowed run, else the arguments
         intermediates = {"x_inter": [img], "pred_x0": [img]}
@@ -157,6 +160,8 @@ class DPMSolverSampler(SamplerBase):
         for i in range(total_steps):
             if mask is not None:
                 # img = q_sample(x0, ts)*mask + (1-mask)*img, between the replays; its draw comes first
+                if plan.level_d is not None:   # graded keep levels: this step's binary mask from the level map
+                    ops.keep_threshold_indexed(plan.level_d, plan.keep_thr[i:i + 1], plan.mask_d)
                 ops.inpaint_blend(x_cur, plan.x0_d, draw().to(dev), plan.mask_d, plan.blend_coef[i])
             if qbuf is not None:
                 qbuf.copy_(draw())   # the same draw; the blend itself is a node of the step

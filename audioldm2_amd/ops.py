@@ -1677,6 +1677,28 @@ def renoise_indexed(x: torch.Tensor, noise_tab: torch.Tensor, coef_tab: torch.Te
     return x
 
 
+def keep_threshold_indexed(level: torch.Tensor, thr_tab: torch.Tensor, mask: torch.Tensor,
+                           step_idx: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The binary mask of a step from a map of keep levels (aldm_keep_threshold_indexed; differential diffusion):
+    mask = 1.0 where level > thr_tab[r], else 0.0, r the int32 device counter `step_idx` clamped into the table (None: row 0).
+    level and mask have one shape and share no byte; thr_tab [V] is a run's threshold table (sampling.keep_thresholds), one entry
+    per visit.  A NaN level gives 0.  Issued directly in front of a step's blend, which reads `mask`.  -> mask."""
+    for t, n in ((level, "level"), (thr_tab, "thr_tab"), (mask, "mask")):
+        _chk(t, "keep_threshold." + n)
+    if level.numel() == 0 or tuple(mask.shape) != tuple(level.shape):
+        raise RuntimeError(f"keep_threshold.mask: expected {tuple(level.shape)} (the levels' shape, not empty), got "
+                           f"{tuple(mask.shape)}")
+    if thr_tab.dim() != 1 or thr_tab.numel() == 0:
+        raise RuntimeError(f"keep_threshold.thr_tab: expected a [V] table, got {tuple(thr_tab.shape)}")
+    if step_idx is not None and not (step_idx.dtype == torch.int32 and step_idx.is_cuda and step_idx.numel() == 1):
+        raise RuntimeError(f"keep_threshold.step_idx: expected one int32 CUDA element, got {step_idx.dtype} {step_idx.device} "
+                           f"numel={step_idx.numel()}")
+    _no_overlap(mask, "keep_threshold.mask", [(level, "level")])
+    _l.check(_l.load().aldm_keep_threshold_indexed(level.data_ptr(), thr_tab.data_ptr(), _p(step_idx), thr_tab.shape[0],
+                                                   mask.data_ptr(), level.numel(), _stream()), "keep_threshold_indexed")
+    return mask
+
+
 def posterior_qsample(moments_cl: torch.Tensor, n_post: torch.Tensor, n_enc: torch.Tensor, coef: torch.Tensor,
                       z: Optional[torch.Tensor] = None, x_t: Optional[torch.Tensor] = None):
     """The VAE posterior sample and its forward diffusion in one launch (aldm_posterior_qsample): moments_cl [B0, h, w, 2C]

@@ -427,6 +427,15 @@ RESAMPLE_MULTISTEP = ("resample= (resampled inpainting) runs on the DDIM sampler
                       "DPM-Solver++(2M) does not survive a jump back to a higher noise level")
 
 
+def _is_graded(keep, feather):
+    """True when a `keep` list / `feather` pair has to go through windows.keep_levels: an interval with a third
+    element, or a feather that is not the integer 0 (a malformed one included, which keep_levels refuses).  Pairs with feather 0
+    are the plain keep: windows.keep_mask, today's call, unchanged."""
+    if isinstance(feather, bool) or not isinstance(feather, (int, np.integer)) or feather != 0:
+        return True
+    return any(hasattr(iv, "__len__") and len(iv) >= 3 for iv in keep)
+
+
 def check_resample_job(resample, ddim_steps, sampler, use_plms, ld):
     """The `resample=(n, jump)` keyword of the jobs that keep a source (generate_batch_masked, generate_batch_long_from_audio,
     extend_audio), host only, before anything is drawn: None, or RePaint's pair checked against the sampler and the `ddim_steps`
@@ -739,6 +748,15 @@ class LatentDiffusion(nn.Module):
             if mask is None and kwargs.get("x0", None) is None and getattr(windows, "x0", None) is None:
                 raise ValueError("resample= needs something to harmonise with: a mask / x0, or a source on the window plan "
                                  "(windows.with_source)")
+        # `graded` (a keyword of **kwargs: `mask` is a map of keep levels in [0, 1], graded keep) goes to whichever of
+        # the three samplers runs; a source on the window plan carries its own flag (windows.with_source)
+        if not kwargs.get("graded", False):
+            kwargs.pop("graded", None)   # absent: today's call, unchanged
+        else:
+            from .sampling import check_levels
+            if not (use_plms or sampler_name is not None or ddim):
+                raise ValueError("graded=True needs ddim_steps: the ancestral sampler has no graded keep levels")
+            check_levels(mask, kwargs.get("x0", None))
         if mask is not None:
             shape = (self.channels, mask.size()[-2], mask.size()[-1])
         elif windows is not None:
@@ -1022,12 +1040,21 @@ class LatentDiffusion(nn.Module):
     def generate_batch_masked(self, batch, ddim_steps=200, ddim_eta=1.0, x_T=None, n_gen=1,
                               unconditional_guidance_scale=1.0, unconditional_conditioning=None,
                               use_plms=False, time_mask_ratio_start_and_end=(0.25, 0.75),
-                              freq_mask_ratio_start_and_end=(0.75, 1.0), **kwargs):
+                              freq_mask_ratio_start_and_end=(0.75, 1.0), levels=None, **kwargs):
         """ddpm.py:1573-1676 (inpainting / super-resolution): VAE-encode the given mel -> x0, keep the
         unmasked latent region (DDIM blends q_sample(x0, t) back in every step), regenerate the rest.
         `resample=(n, jump)` (a keyword of **kwargs like `sampler`): resampled inpainting — RePaint's jumps back to a
-        higher noise level, so the generated region is re-made in the presence of the kept one; DDIM only, refused before any draw."""
+        higher noise level, so the generated region is re-made in the presence of the kept one; DDIM only, refused before any draw.
+        `levels`: a tensor of keep levels in [0, 1], broadcastable to [B, 1, h, w] of the latent, in place of the
+        ratio-built mask — graded keep over time AND frequency at the trained length: a cell of level m is held on the noised
+        source for its first sampling.hold_steps(m, steps) steps and is free afterwards.  Needs ddim_steps; bad values are refused
+        before any draw, a shape that does not broadcast once the latent's size is known."""
         assert x_T is None
+        if levels is not None:
+            from .sampling import check_levels
+            if ddim_steps is None:
+                raise ValueError("levels= needs ddim_steps: the ancestral sampler has no graded keep levels")
+            check_levels(levels, levels, "generate_batch_masked(levels=)")
         sampler = resolve_sampler(kwargs.get("sampler", None), use_plms)
         neg_batch, guidance_rescale = _guidance_kwargs(kwargs, unconditional_guidance_scale, batch, ddim_steps)
         resample = check_resample_job(kwargs.get("resample", None), ddim_steps, sampler, use_plms, self)
@@ -1048,6 +1075,13 @@ class LatentDiffusion(nn.Module):
         mask[:, int(h * time_mask_ratio_start_and_end[0]):int(h * time_mask_ratio_start_and_end[1]), :] = 0
         mask[:, :, int(w * freq_mask_ratio_start_and_end[0]):int(w * freq_mask_ratio_start_and_end[1])] = 0
         mask = mask[:, None, ...]
+        graded_kw = {}
+        if levels is not None:
+            try:
+                mask = levels.detach().float().to(self.device).expand(batch_size, 1, h, w).contiguous()
+            except RuntimeError:
+                raise ValueError(f"levels= must broadcast to [B, 1, h, w] = {(batch_size, 1, h, w)}, got {tuple(levels.shape)}")
+            graded_kw["graded"] = True
         c = _tile_cond(c, n_gen)
         text = list(batch["text"]) * n_gen
         unconditional_conditioning = _unconditional_half(self, neg_batch, n_gen, batch_size, unconditional_guidance_scale,
@@ -1055,7 +1089,7 @@ class LatentDiffusion(nn.Module):
         samples, _ = self.sample_log(cond=c, batch_size=batch_size, x_T=x_T, ddim=use_ddim, ddim_steps=ddim_steps,
                                      eta=ddim_eta, unconditional_guidance_scale=unconditional_guidance_scale,
                                      unconditional_conditioning=unconditional_conditioning, use_plms=use_plms,
-                                     mask=mask, x0=torch.cat([z] * n_gen),
+                                     mask=mask, x0=torch.cat([z] * n_gen), **graded_kw,
                                      **_sample_log_keywords(sampler, guidance_rescale, resample=resample))
         return _waveform_of(self, samples, batch, text, n_gen, B0)
 
@@ -1256,7 +1290,7 @@ class LatentDiffusion(nn.Module):
     def generate_batch_long_from_audio(self, batch, latent_t_size, keep, hop=None, ddim_steps=200, ddim_eta=1.0,
                                        unconditional_guidance_scale=1.0, use_plms=False, sampler=None, negative_prompt=None,
                                        guidance_rescale=0.0, n_gen=1, shard=None, loop=False, boundaries=None, transition=0.0,
-                                       resample=None):
+                                       feather=0, resample=None):
         """Continuation and inpainting of long clips: generate_batch_long around a source.  `batch["log_mel_spec"]`
         is the long mel [B0, latent_t_size*f, F_mel] of the source; `keep` lists the half-open latent-frame intervals [a, b) to
         keep (windows.keep_mask); everything else is generated under the prompt.  The source is encoded window by window
@@ -1282,8 +1316,16 @@ class LatentDiffusion(nn.Module):
         blend-and-gather — on a linear, a ring and a row plan alike.  DDIM only; n = 1 is the job without the keyword.  The job
         runs V_step / ddim_steps times as many UNet steps and holds two noise tables of V rows at the long latent's size.
 
+        Graded keep (differential diffusion, Levin & Fried 2023): an interval may be (a, b, level) with
+        0 < level <= 1, and `feather` (latent frames) fades every interval out over that many frames on either side
+        (windows.keep_levels; round the circle with loop=True).  A frame of level m is held on the noised source for its first
+        sampling.hold_steps(m, steps) steps and is free afterwards — SDEdit at strength about 1 - m on that frame alone, in the
+        context of its neighbours; level 1 is the plain keep, level 0 the plain generate.  One more launch per step
+        (aldm_keep_threshold_indexed) thresholds the level map into the binary mask the blend reads; the draws do not change, and
+        timelines and `resample` work as before.  With every level 1 and feather == 0 the job is exactly the one without them.
+
         Refused before any draw or GPU work: ddim_steps=None, n_gen != 1, shard=, bad lengths or hops (long_form_plans), a bad
-        `keep`, a mel whose length is not latent_t_size*f, a bad timeline (generate_batch_long), a bad `resample` (a malformed pair,
+        `keep` or `feather`, a mel whose length is not latent_t_size*f, a bad timeline (generate_batch_long), a bad `resample` (a malformed pair,
         n < 1, jump outside [1, steps - 1], together with use_plms=True or sampler="dpmpp_2m").
 
         Host-generator order (RNG contract R): (R1) randn(B0, C, latent_t_size, F) at the LONG shape, the
@@ -1292,7 +1334,7 @@ class LatentDiffusion(nn.Module):
         shape: DDIM the q-noise then the step noise, PLMS the q-noise then its own draws, DPM-Solver++ the q-noise only.  A timeline:
         the conditioners' draws once per prompt in timeline order, then the negative prompt's.  With `resample`, "per step" reads
         "per visit": the same two draws for each of the V visits, a renoise visit's q-noise drawn and not read."""
-        from .windows import keep_mask, with_source
+        from .windows import keep_levels, keep_mask, with_source
         batches, batch = _timeline_batches(batch, boundaries, loop, "generate_batch_long_from_audio")
         if shard is not None:
             raise ValueError("generate_batch_long_from_audio: shard= is not supported on this path")
@@ -1308,7 +1350,10 @@ class LatentDiffusion(nn.Module):
         resample = check_resample_job(resample, ddim_steps, sampler, use_plms, self)
         plan, mel_plan = self.long_form_plans(latent_t_size, hop)
         ring_plans = self.long_form_plans(latent_t_size, hop, ring=True) if loop else None   # refuses a bad ring before any draw
-        mask_t = keep_mask(plan.T, keep)
+        graded = _is_graded(keep, feather)
+        mask_t = keep_levels(plan.T, keep, feather, ring=bool(loop)) if graded else keep_mask(plan.T, keep)
+        # every level 1 and nothing feathered (a triple of level 1): exactly the call without levels
+        graded = graded and not torch.equal(mask_t, keep_mask(plan.T, [tuple(iv)[:2] for iv in keep]))
         run_plan = plan if batches is None else _timeline_row_plan(plan, boundaries, transition)   # refuses, host only
         fb = batch["log_mel_spec"] if self.first_stage_key == "fbank" else batch[self.first_stage_key]
         f = 2 ** (self.first_stage_model.encoder.num_resolutions - 1)
@@ -1328,7 +1373,8 @@ class LatentDiffusion(nn.Module):
         samples, _ = self.sample_log(cond=c, batch_size=B0, x_T=None, ddim=True, ddim_steps=ddim_steps, eta=ddim_eta,
                                      unconditional_guidance_scale=unconditional_guidance_scale,
                                      unconditional_conditioning=unconditional_conditioning, use_plms=use_plms,
-                                     windows=with_source(run_plan, z, mask_t),
+                                     windows=with_source(run_plan, z, mask_t, graded=True) if graded
+                                     else with_source(run_plan, z, mask_t),
                                      **_sample_log_keywords(sampler, guidance_rescale, resample=resample))
         return self._long_tail(samples, plan, mel_plan, batch)
 
@@ -1652,24 +1698,27 @@ def _source_seconds(source):
 
 def keep_frames(keep, per_second, latent_t):
     """Pure host: `keep` intervals (start_s, end_s) in seconds -> half-open latent-frame intervals [ceil(start*fps),
-    floor(end*fps)), the frames that lie wholly inside the interval, the end clipped to `latent_t`.  ValueError for an interval
-    that is not a pair of finite numbers; windows.keep_mask refuses what is empty, unordered, overlapping or out of range."""
+    floor(end*fps)), the frames that lie wholly inside the interval, the end clipped to `latent_t`.  A third element (a keep
+    level) passes through untouched: pairs stay pairs, triples stay triples.  ValueError for an interval that is
+    not a pair of finite numbers (with or without a level); windows.keep_mask / keep_levels refuse what is empty, unordered,
+    overlapping or out of range, and a bad level."""
     out = []
     for iv in keep:
         try:
-            a, b = (float(v) for v in iv)
+            level = tuple(iv[2:]) if len(iv) == 3 else ()
+            a, b = (float(v) for v in (iv[:2] if level else iv))
         except (TypeError, ValueError):
             raise ValueError(f"keep: an interval must be a pair (start_s, end_s) of seconds, got {iv!r}")
         if not (np.isfinite(a) and np.isfinite(b)):
             raise ValueError(f"keep: interval bounds must be finite, got {iv!r}")
         # 1e-9 of a frame: a bound that is a whole frame in exact arithmetic (5 s at 25.6 frames per second) stays that frame
-        out.append((int(math.ceil(a * per_second - 1e-9)), min(int(math.floor(b * per_second + 1e-9)), int(latent_t))))
+        out.append((int(math.ceil(a * per_second - 1e-9)), min(int(math.floor(b * per_second + 1e-9)), int(latent_t))) + level)
     return out
 
 
 def extend_audio(latent_diffusion, text, original_audio_file_path, duration, keep=None, overlap=2.5, transcription="", seed=42,
                  ddim_steps=200, guidance_scale=3.5, sampler=None, negative_prompt=None, guidance_rescale=0.0, loop=False,
-                 timeline=None, transition=0.0, resample=None):
+                 timeline=None, transition=0.0, feather=0.0, resample=None):
     """Continue or inpaint a long clip: a clip of `duration` seconds — longer than the model's trained length — that keeps parts
     of the recording `original_audio_file_path` (a path, or a 1-D float waveform at 16 kHz; zero-padded or cut to `duration`) and
     generates the rest under the prompt `text` by windowed diffusion (LatentDiffusion.generate_batch_long_from_audio).  `keep`
@@ -1689,9 +1738,16 @@ def extend_audio(latent_diffusion, text, original_audio_file_path, duration, kee
     DDIM only; the job runs (steps + (n - 1) * jump * points) / steps times as long.  With `keep=[...]` this is resampled inpainting
     at any duration from the trained length up; the reference-API route at the trained length is
     LatentDiffusion.generate_batch_masked(..., resample=...).
+    Graded keep (differential diffusion): an interval may be (start_s, end_s, level) with 0 < level <= 1, and
+    `feather` (seconds; int(round(feather * fps)) latent frames) fades every kept interval into the generated part over that long
+    on either side — round the junction with loop=True.  A frame of level m is held on the noised source for about the first
+    m * steps steps (sampling.hold_steps) and is free afterwards: about audio_to_audio's strength 1 - m on that frame alone — about,
+    because the two round differently — in the context of its neighbours.  "Keep seconds 0-12, vary 12-15 only a little, make
+    the rest new": keep=[(0, 12), (12, 15, 0.8)].  Vary a long recording, which audio_to_audio cannot: keep=[(0, 30, 0.5)].  One
+    more small launch per step; pairs with feather 0 are exactly the job without levels.
     Returns np.float32 [1, 1, samples]."""
     from .stft import TacotronSTFT
-    from .windows import keep_mask
+    from .windows import keep_levels, keep_mask
     sampler_kw = _sampler_kwargs(sampler, negative_prompt, guidance_rescale)
     if ddim_steps is None:
         raise ValueError("extend_audio needs ddim_steps: the ancestral sampler has no windowed form")
@@ -1715,7 +1771,17 @@ def extend_audio(latent_diffusion, text, original_audio_file_path, duration, kee
     if keep is None:
         keep = [(0.0, min(_source_seconds(original_audio_file_path), float(duration)))]
     frames = keep_frames(keep, per_second, latent_t)
-    keep_mask(latent_t, frames)   # refuse a bad keep before any draw
+    try:
+        feather_frames = int(round(float(feather) * per_second))
+        if isinstance(feather, bool) or not np.isfinite(float(feather)) or feather < 0:
+            raise ValueError
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(f"extend_audio: feather must be a finite, non-negative number of seconds, got {feather!r}")
+    # refuse a bad keep or feather before any draw
+    if _is_graded(frames, feather_frames):
+        keep_levels(latent_t, frames, feather_frames, ring=bool(loop))
+    else:
+        keep_mask(latent_t, frames)
     seed_everything(int(seed))
     fn_STFT = TacotronSTFT(1024, 160, 1024, 64, 16000, 0, 8000)  # utils.py:262-270 "preprocessing"
     mel, _, _ = wav_to_fbank(original_audio_file_path, target_length=latent_t * f, fn_STFT=fn_STFT)
@@ -1725,7 +1791,8 @@ def extend_audio(latent_diffusion, text, original_audio_file_path, duration, kee
     with torch.no_grad():
         return latent_diffusion.generate_batch_long_from_audio(batch, latent_t, frames, hop=hop,
                                                                unconditional_guidance_scale=guidance_scale,
-                                                               ddim_steps=ddim_steps, loop=loop, **sampler_kw, **tl_kw)
+                                                               ddim_steps=ddim_steps, loop=loop, feather=feather_frames,
+                                                               **sampler_kw, **tl_kw)
 
 
 def audio_to_audio(latent_diffusion, text, original_audio_file_path, strength=0.5, transcription="", seed=42,

@@ -42,6 +42,7 @@ class PLMSSampler(SamplerBase):
         super().__init__(model, schedule)
         self.t_start = None   # sampler state like guidance_rescale: `sample` sets it on every call, `plms_sampling` reads it
         self.windows = None   # the same way: a windows.window_plan over the long latent (`windows=`), or None
+        self.graded = False   # the same way: `mask` is a map of keep levels in [0, 1] (`graded=`)
         # phi of Lin et al. 2023 (section 3.4), 0: off.  Sampler state like the schedule, not a parameter: `plms_sampling` and
         # `p_sample_plms` keep the reference class's signatures, which have no **kwargs to take it.  `sample` sets it on every
         # call from its `guidance_rescale=` keyword (absent: 0); a caller of the two other methods sets the attribute.
@@ -72,6 +73,7 @@ class PLMSSampler(SamplerBase):
         # like `guidance_rescale`, and becomes `self.t_start` for this run
         self.t_start = check_t_start(kwargs.pop("t_start", None), kwargs.get("timesteps"), len(self.ddim_timesteps))
         self.windows = kwargs.pop("windows", None)   # the same way: windowed diffusion over the long `shape` (SamplerBase.plan_run)
+        self.graded = bool(kwargs.pop("graded", False))   # the same way: `mask` holds keep levels (SamplerBase.plan_run)
         C, H, W = shape
         size = (batch_size, C, H, W)
         return self.plms_sampling(conditioning, size, callback=callback, img_callback=img_callback,
@@ -98,7 +100,8 @@ class PLMSSampler(SamplerBase):
         plan = self.plan_run(cond, shape, x_T, self.t_start, timesteps,
                              lambda n, cfg: guidance_table(self.plms_coef[:n].flip(0), unconditional_guidance_scale, cfg,
                                                            guidance_rescale),
-                             unconditional_guidance_scale, unconditional_conditioning, guidance_rescale, mask, x0, self.windows)
+                             unconditional_guidance_scale, unconditional_conditioning, guidance_rescale, mask, x0, self.windows,
+                             graded=self.graded)
         total_steps, use_cfg, rescale, draw, img = plan.total_steps, plan.use_cfg, plan.rescale, plan.draw, plan.img
         cond, unconditional_conditioning, win = plan.cond, plan.uncond, plan.win   # tiled W times in a windowed run
         intermediates = {"x_inter": [img], "pred_x0": [img]}
@@ -138,6 +141,8 @@ class PLMSSampler(SamplerBase):
         for i in range(total_steps):
             if mask is not None:
                 # img = q_sample(x0, ts)*mask + (1-mask)*img   (plms.py:222-227, ddpm.py:430-436); its draw comes first
+                if plan.level_d is not None:   # graded keep levels: this step's binary mask from the level map
+                    ops.keep_threshold_indexed(plan.level_d, plan.keep_thr[i:i + 1], plan.mask_d)
                 ops.inpaint_blend(x_cur, plan.x0_d, draw().to(dev), plan.mask_d, plan.blend_coef[i])
             if qbuf is not None:
                 qbuf.copy_(draw())   # the same draw, first in the step; the blend itself runs inside the step's first pass

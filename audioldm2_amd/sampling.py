@@ -11,7 +11,9 @@ run that is the same whichever update rule runs.
   * host_drawer / _NoiseFeed: the host generator's draws in the reference's order (RNG contract, SURVEY.md §8 row R);
   * check_guidance_rescale / check_t_start: the two per-run options every sampler takes; log_step: the tail of every step;
   * resample_visits / renoise_coef / check_resample: the visit schedule and the forward-jump coefficients of resampled inpainting
-    (RePaint's jumps, `resample=(n, jump)`), which plan_run turns into per-visit tables for DDIM's loop.
+    (RePaint's jumps, `resample=(n, jump)`, DESIGN.md 9i), which plan_run turns into per-visit tables for DDIM's loop;
+  * keep_thresholds / hold_steps / check_levels: the per-step thresholds of graded keep levels (`graded=True`, differential
+    diffusion) and what a level means in steps; plan_run keeps the level map and the threshold rows on the device.
 
 What differs between the samplers stays in their modules: DDIM's graph cache on the UNet and its threaded noise feed, PLMS's eager
 Euler step 0 and its discarded `noise_like` draws, DPM-Solver++'s table per sub-range.  ddim.py re-exports every name that lived
@@ -391,6 +393,38 @@ def check_resample(resample, S=None):
     return int(n), int(jump)
 
 
+def keep_thresholds(S, visits=None):
+    """Pure host function: the threshold table of graded keep levels (differential diffusion, Levin & Fried 2023)
+    over a run of S sampler steps -> fp32 [S], entry i = float32(i / S), the quotient taken in fp64.  At loop step i a frame of
+    level m is held on q_sample(source, t_i) when float32(m) > entry i, and is free otherwise: level 1 is held at every step, level
+    0 at none.  `visits` (resample_visits): one row per visit instead — a step visit takes its loop position's entry, a renoise
+    visit the next step visit's, which is not read (plan_run fills blend_coef the same way)."""
+    if not _integer(S) or S < 1:
+        raise ValueError(f"keep_thresholds: the run must have a positive integer number of steps, got {S!r}")
+    pos = np.arange(int(S)) if visits is None else np.asarray([v[1] if v[0] == "step" else v[2] for v in visits])
+    return torch.from_numpy((pos.astype(np.float64) / float(int(S))).astype(np.float32))
+
+
+def hold_steps(level, S):
+    """Pure host function: what a keep level MEANS in a run of S steps — the number of loop steps i < S at which a frame of that
+    level is held on the noised source, float32(level) > keep_thresholds(S)[i], compared in fp32 (equality releases the frame).
+    The thresholds ascend, so these are the run's FIRST hold_steps steps; the frame is free for its last S - hold_steps.  S is
+    the number of steps the run really makes (after a t_start / timesteps cut)."""
+    return int((np.float32(level) > keep_thresholds(S).numpy()).sum())
+
+
+def check_levels(mask, x0, who="graded=True"):
+    """graded=True declares a sampler's mask a map of keep levels: it needs a mask and a source, and every level finite and in [0, 1].
+    ValueError otherwise; host only for a host mask."""
+    if mask is None or x0 is None:
+        raise ValueError(f"{who} needs a mask of keep levels and a source x0 (or both on the window plan, windows.with_source)")
+    if not torch.is_tensor(mask):
+        raise ValueError(f"{who}: the levels must be a tensor, got {type(mask).__name__}")
+    m = mask.detach().float()
+    if m.numel() == 0 or not bool(torch.isfinite(m).all()) or float(m.min()) < 0.0 or float(m.max()) > 1.0:
+        raise ValueError(f"{who}: keep levels must be finite and lie in [0, 1]")
+
+
 def ddim_step_rows(sigmas, alphas, alphas_prev, sqrt_one_minus_alphas):
     """Pure host function: the [S, 5] fp32 rows {sqrt(1 - a_t), sqrt(a_t), sqrt(1 - a_prev - sigma_t^2), sqrt(a_prev), sigma_t} of
     DDIM's update (the row layout of ops.ddim_step), one per schedule index, with the reference's roundings (ddim.py:330-353,
@@ -494,6 +528,10 @@ class SamplerBase(object):
         if win is not None:
             if win.blend and first_pass:
                 # a plan with a source: the blend of the known region on the long latent, in place, and the gather are one launch
+                if getattr(win, "level", None) is not None:
+                    # graded keep levels: this step's binary mask from the level map, one launch in front of the
+                    # blend, reading the same counter — a node of the captured step like the blend itself
+                    ops.keep_threshold_indexed(win.level, win.keep_thr, win.mask, win.step_idx)
                 xw = ops.window_blend_gather(x, win.x0, win.qnoise, win.mask, win.blend_coef, win.plan, step_idx=win.step_idx,
                                              out=win.xw if static else None)
             else:
@@ -508,7 +546,7 @@ class SamplerBase(object):
         return torch.stack([self.model.apply_model(x, tl, uncond), self.model.apply_model(x, tl, cond)]).contiguous()
 
     def plan_run(self, cond, shape, x_T, t_start, timesteps, table, unconditional_guidance_scale, unconditional_conditioning,
-                 guidance_rescale, mask, x0, windows=None, resample=None):
+                 guidance_rescale, mask, x0, windows=None, resample=None, graded=False):
         """Everything a sampling loop needs before its first step, as one object.  `table(total_steps, use_cfg)` is the sampler's
         own [total_steps, 8] host coefficient table in loop order (i = 0 is the noisiest step, index = total_steps - 1).
 
@@ -536,9 +574,16 @@ class SamplerBase(object):
         Refused (ValueError) before the first draw: a malformed pair or values resample_visits refuses, and a run with nothing to
         harmonise with (no mask / x0 and no source on the plan).  n == 1 is the plain run: p.visits is None, as without the keyword.
 
+        `graded` (or a plan whose source was declared graded, windows.with_source): the mask is a map of keep LEVELS
+        in [0, 1].  p.level_d holds the expanded map, p.mask_d becomes a scratch buffer of the same shape — what the blend reads,
+        as always — and p.keep_thr the run's threshold rows on the device (keep_thresholds over the cut schedule, one per visit);
+        p.win carries `level` and `keep_thr` too.  The sampler issues ops.keep_threshold_indexed directly in front of every blend.
+        Refused (ValueError) before the first draw: no mask or source, levels that are not finite or leave [0, 1].  Without it
+        p.level_d and p.keep_thr are None and nothing changes.
+
         RNG contract R: x_T is the host generator's first draw of the run, made only when x_T is not given; `draw` makes the
         loop's later ones.  A start latent that already lives on the device (audio-to-audio) stays there.  Host -> device copies,
-        in this order: img, coef, t_tab, mask_d, x0_d, blend_coef, then the model's prepare_cfg."""
+        in this order: img, coef, t_tab, mask_d, x0_d, blend_coef, keep_thr, then the model's prepare_cfg."""
         dev = torch.device("cuda")
         shape = tuple(shape)
         from .windows import check_per_prompt, has_rows
@@ -555,6 +600,9 @@ class SamplerBase(object):
                 if tuple(windows.x0.shape) != shape:
                     raise ValueError(f"windows=: the plan's source x0 is {tuple(windows.x0.shape)}, the latent shape is {shape}")
                 source = (windows.mask, windows.x0)
+                graded = bool(graded) or bool(getattr(windows, "graded", False))
+        if graded:
+            check_levels(*(source if source is not None else (mask, x0)))
         ts = self.ddim_timesteps
         t_start = check_t_start(t_start, timesteps, ts.shape[0])
         if t_start is not None:
@@ -565,7 +613,7 @@ class SamplerBase(object):
         total_steps = ts.shape[0]
         use_cfg = not (unconditional_conditioning is None or unconditional_guidance_scale == 1.0)
         p = SimpleNamespace(total_steps=total_steps, use_cfg=use_cfg, mask_d=None, x0_d=None, blend_coef=None, prepared=None,
-                            cond=cond, uncond=unconditional_conditioning, win=None, visits=None)
+                            cond=cond, uncond=unconditional_conditioning, win=None, visits=None, level_d=None, keep_thr=None)
         if resample is not None:
             if mask is None and x0 is None and source is None:
                 raise ValueError("resample= needs something to harmonise with: a mask / x0, or a source on the window plan "
@@ -603,6 +651,10 @@ class SamplerBase(object):
             p.x0_d = x0.float().to(dev).contiguous()
             p.blend_coef = torch.stack([self.sqrt_alphas_cumprod[tr], self.sqrt_one_minus_alphas_cumprod[tr]],
                                        1).contiguous().to(dev)  # [S, 2] = {sqrt(abar_t), sqrt(1 - abar_t)}
+            if graded:
+                # the map of levels stays; the blend's mask is rewritten from it in front of every blend (keep_threshold_indexed)
+                p.level_d, p.mask_d = p.mask_d, torch.zeros_like(p.mask_d)
+                p.keep_thr = keep_thresholds(total_steps, p.visits).to(dev)
         if windows is not None:
             from .windows import rows_cond, tile_cond
             p.cond = rows_cond(cond, windows) if has_rows(windows) else tile_cond(cond, W)
@@ -613,7 +665,7 @@ class SamplerBase(object):
             p.win = SimpleNamespace(plan=windows, xw=torch.empty((W * b, C, windows.Tw, F), device=dev, dtype=torch.float32),
                                     merged=torch.empty(((2,) if use_cfg else ()) + shape, device=dev, dtype=torch.float32),
                                     blend=source is not None, x0=p.x0_d, mask=p.mask_d, blend_coef=p.blend_coef, qnoise=None,
-                                    step_idx=None, n=W,
+                                    step_idx=None, n=W, level=p.level_d, keep_thr=p.keep_thr,
                                     # a row plan: the merge's [R, Tw] weights, a static buffer of the run (of the step graph's
                                     # cache entry, which refills it per job: two timelines of one row geometry share a graph)
                                     wr=windows.wr.to(dev).contiguous() if has_rows(windows) else None)

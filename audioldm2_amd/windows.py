@@ -6,7 +6,8 @@ tapered, normalised overlap-add (ops.window_merge) before the sampler's update o
 kernels need: the window starts and the normalised weights.
 
 A plan may carry a source to keep (`with_source`, `keep_mask`): continuation and inpainting of long clips.  The
-samplers then blend q_sample(source, t) into the long latent in front of every step's gather (ops.window_blend_gather).
+samplers then blend q_sample(source, t) into the long latent in front of every step's gather (ops.window_blend_gather).  The mask
+may be a map of keep LEVELS (`keep_levels`, `with_source(..., graded=True)`): the samplers threshold it per step.
 
 A linear plan may carry a prompt timeline (`prompt_weights`, `row_plan`, `PerPrompt`, `rows_cond`): every prompt has a
 weight per latent frame, a window that sees several prompts becomes one ROW per prompt, the UNet runs on the rows — each under its
@@ -309,12 +310,58 @@ def keep_mask(T, intervals):
     return m
 
 
-def with_source(plan, x0, mask):
+def keep_levels(T, intervals, feather=0, ring=False):
+    """The [T] fp32 vector of a source's keep LEVELS (graded keep, differential diffusion): a frame of level m is
+    held on the noised source for about the first m*S of a run's S steps and is free afterwards (sampling.hold_steps) — 1 is
+    keep_mask's keep, 0 its generate.  `intervals`: (a, b) or (a, b, level), half-open latent-frame intervals under keep_mask's
+    rules (integers, 0 <= a < b <= T, ascending, may touch, may not overlap), level a finite number with 0 < level <= 1, default 1.
+    Inside an interval the value is its level.  `feather` (an integer, 0 <= feather < T) fades every interval out over that many
+    frames on either side: a frame outside every interval, at distance d from interval I (d = a - t left of it, t - (b - 1) right
+    of it; with ring=True the shorter way round the circle of T frames), gets max over I of level_I * max(0, 1 - d / (feather + 1)).
+    fp64, rounded to fp32 once.  With every level 1 and feather == 0 the result is keep_mask(T, intervals).  ValueError otherwise."""
+    T = _check_int(T, "T")
+    if isinstance(feather, bool) or not isinstance(feather, (int, np.integer)) or not 0 <= feather < T:
+        raise ValueError(f"keep_levels: feather must be an integer number of latent frames in [0, T={T}), got {feather!r}")
+    ivs = []
+    for iv in intervals:
+        try:
+            n = len(iv)
+        except TypeError:
+            n = 0
+        if n not in (2, 3):
+            raise ValueError(f"keep_levels: an interval must be (start, end) or (start, end, level), got {iv!r}")
+        level = 1.0
+        if n == 3:
+            level = iv[2]
+            if isinstance(level, (bool, np.bool_)) or not isinstance(level, (int, float, np.integer, np.floating)) \
+                    or not (np.isfinite(level) and 0.0 < level <= 1.0):
+                raise ValueError(f"keep_levels: a level must be a finite number in (0, 1], got {iv!r}")
+        ivs.append((iv[0], iv[1], float(level)))
+    keep_mask(T, [iv[:2] for iv in ivs])   # the intervals themselves: keep_mask's rules and messages (integer bounds from here on)
+    t = np.arange(T, dtype=np.int64)
+    out = np.zeros(T, dtype=np.float64)
+    for a, b, level in ivs:
+        left, right = a - t, t - (b - 1)
+        if ring:
+            d = np.minimum(left % T, right % T)
+        else:
+            d = np.where(t < a, left, right)
+        inside = (t >= a) & (t < b)
+        v = level * np.maximum(0.0, 1.0 - d.astype(np.float64) / (int(feather) + 1.0))
+        out = np.maximum(out, np.where(inside, 0.0, v))
+    for a, b, level in ivs:
+        out[a:b] = level
+    return torch.from_numpy(out.astype(np.float32))
+
+
+def with_source(plan, x0, mask, graded=False):
     """`plan` with a source to keep (continuation and inpainting of long clips): a plan object with the same T, Tw,
     starts, ring flag and wn — and so the same plan_key — that additionally carries `x0` [b, C, T, F] (the source's scaled latent)
     and `mask` (broadcastable to x0's shape; 1 = keep the source, 0 = generate; a [T] vector, as keep_mask returns it, is taken along the time
     axis).  A sampler given such a plan as `windows=` blends q_sample(x0, t) into the long latent in front of every step's gather
-    (ops.window_blend_gather).  ValueError for shapes that do not fit plan.T."""
+    (ops.window_blend_gather).  `graded=True` declares the mask a map of keep LEVELS in [0, 1] (keep_levels): the
+    sampler thresholds it per step into the binary mask the blend reads; the flag rides on the plan, the plan_key is unchanged.
+    ValueError for shapes that do not fit plan.T."""
     if not torch.is_tensor(x0) or x0.dim() != 4 or x0.shape[2] != plan.T:
         raise ValueError(f"with_source: x0 must be a tensor [b, C, T={plan.T}, F], got "
                          f"{tuple(x0.shape) if torch.is_tensor(x0) else type(x0).__name__}")
@@ -330,7 +377,7 @@ def with_source(plan, x0, mask):
         ok = False
     if not ok:
         raise ValueError(f"with_source: mask {tuple(mask.shape)} does not broadcast to x0 {tuple(x0.shape)}")
-    return SimpleNamespace(**dict(plan.__dict__, x0=x0, mask=mask))
+    return SimpleNamespace(**dict(plan.__dict__, x0=x0, mask=mask, graded=bool(graded)))
 
 
 def device_weights(plan, device):

@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 /* ---- library / error ------------------------------------------------------------------ */
-int aldm_version(void);              /* ABI version (23), bumped on any struct / entry change */
+int aldm_version(void);              /* ABI version (24),bumped on any struct / entry change */
 const char* aldm_last_error(void);   /* message of the last failing call on this thread     */
 
 /* ---- activations usable as prologue (applied to the gathered input) or epilogue -------- */
@@ -586,6 +586,16 @@ int aldm_inpaint_blend(const float* x0, const float* qnoise, const float* mask, 
  * not cross this ABI).  No atomics, nothing kept between launches.                                                              */
 int aldm_renoise_indexed(float* x, const float* noise_tab, const float* coef_tab, const int* step_idx, int64_t n, int coef_ld,
                          void* stream);
+/* Graded keep levels (differential diffusion, Levin & Fried 2023, "change maps"; ABI v24): the binary mask a step's
+ * blend reads, rewritten per step from a map of levels in [0, 1]:
+ *   r = clamp(step_idx ? *step_idx : 0, 0, rows - 1);  mask[i] = level[i] > thr_tab[r] ? 1.0f : 0.0f
+ * — the blend-gather entries' conventions for the counter (negative: row 0, past the end: the last row, null: row 0).  thr_tab holds
+ * `rows` floats, one per visit of the run (sampling.keep_thresholds: i / S).  Exactly the bit patterns of 0.0f and 1.0f are written;
+ * the comparison is ordered, so a NaN level gives 0 and equality releases the frame.  The counter is read, never written.  16-byte
+ * accesses when n % 4 == 0 and level and mask are 16-byte aligned, else a scalar path.  Refused before any launch: null pointers,
+ * n <= 0, rows <= 0, mask overlapping level (in place would destroy the levels).  No atomics, nothing kept between launches.       */
+int aldm_keep_threshold_indexed(const float* level, const float* thr_tab, const int* step_idx, int rows, float* mask, int64_t n,
+                                void* stream);
 /* VAE posterior sample fused with the forward diffusion to the sampler's first noise level (audio-to-audio; ABI v16): one launch
  * from the encoder's channels-last moments (autoencoder.py:103-109, distributions.py:24-41, ddpm.py:793-802, ddim.py:434-449):
  *   moments_cl [B0, hw, 2C] channels-last: mean = channels 0..C-1, logvar = channels C..2C-1
