@@ -4,7 +4,9 @@
 // (one row per window and prompt, the merge weighted per row and frame; §9h).  All are HBM-bound copies with at most `cover` multiply-adds (the blend: five operations) per
 // element: 16-byte accesses along the contiguous F axis where F % 4 == 0 and the pointers are aligned, a scalar path otherwise,
 // grid-stride, 64-bit indexing, fp32.  The window starts travel as a kernel argument (aldm_window_starts, by value): a captured
-// step graph carries them, there is no device table and no copy inside a capture; every index into them is wave-uniform.
+// step graph carries them, there is no device table and no copy inside a capture; every index into them is wave-uniform.  The one
+// device table is the phase table of the `_ring_phased` forms (moving window phases, §9k): one int32 per visit, read with the step
+// counter the graph already advances — a static buffer of the graph, refilled per job outside any capture.
 #include "common.h"
 
 namespace aldm {
@@ -209,6 +211,126 @@ __global__ void window_blend_gather_ring_kernel(float* __restrict__ x, const flo
         *reinterpret_cast<vec*>(x + i * V) = v;
         for (int j = 0; j < W; ++j) {
             int p = t - st.s[j];
+            if (p < 0) p += T;
+            if (p >= Tw) continue;
+            *reinterpret_cast<vec*>(win + (((int64_t)j * B + b) * C + c) * wplane + (int64_t)p * F + fv * V) = v;
+        }
+    }
+}
+
+// ---- moving window phases: a ring plan whose starts are all rotated by a phase the step counter selects -------------
+// Siblings of the three ring kernels; those stay what they were.  A rigid rotation keeps every gap, so the plan's weights hold for
+// every phase.  The phase is chosen ON THE DEVICE: row r = clamp(*step_idx, 0, rows - 1) of the int32 table (step_idx NULL: row 0),
+// phi = clamp(phase_tab[r], 0, T - 1) — out-of-range values clamp, they do not wrap: whatever the table holds the launch stays in
+// its buffers.  Window j then covers the frames (s_j + phi + p) mod T.  phi is wave-uniform and read once per thread, outside the
+// element loop; s_j + phi < 2T, so the rotated start is a compare and a subtract and the kernels below go on as their ring siblings.
+__device__ __forceinline__ int window_phase(const int* __restrict__ phase_tab, const int* __restrict__ step_idx, int rows, int T) {
+    int r = step_idx ? *step_idx : 0;
+    r = r < 0 ? 0 : r;
+    r = r < rows ? r : rows - 1;
+    int phi = phase_tab[r];
+    phi = phi < 0 ? 0 : phi;
+    return phi < T ? phi : T - 1;
+}
+
+__device__ __forceinline__ int phased_start(int s, int phi, int T) {
+    const int e = s + phi;
+    return e >= T ? e - T : e;
+}
+
+// win[(j*B + b), c, p, f] = x[b, c, (s_j + phi + p) mod T, f]: window_gather_ring_kernel from the rotated start.
+template <int V>
+__global__ void window_gather_ring_phased_kernel(const float* __restrict__ x, float* __restrict__ win, aldm_window_starts st,
+                                                 const int* __restrict__ phase_tab, const int* __restrict__ step_idx, int rows, int T,
+                                                 int Tw, int F, int64_t per_row, int64_t total) {
+    typedef typename vec_of<V>::type vec;
+    const int j = blockIdx.y;
+    const int s = phased_start(st.s[j], window_phase(phase_tab, step_idx, rows, T), T);
+    const int64_t src0 = (int64_t)s * F;
+    const int64_t plane = (int64_t)T * F;
+    const int64_t len1 = (int64_t)(Tw < T - s ? Tw : T - s) * F / V;
+    float* dst = win + (int64_t)j * total * V;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t bc = i / per_row, off = i - bc * per_row;
+        const int64_t src = off < len1 ? src0 + off * V : (off - len1) * V;
+        *reinterpret_cast<vec*>(dst + i * V) = *reinterpret_cast<const vec*>(x + bc * plane + src);
+    }
+}
+
+// window_merge_ring_kernel with rotated starts: the windows j in ascending order with p = t - (s_j + phi) mod T (+ T if negative)
+// < Tw — the ring merge's result rolled by +phi along T, term for term.
+template <int V>
+__global__ void window_merge_ring_phased_kernel(const float* __restrict__ win, const float* __restrict__ wn, float* __restrict__ out,
+                                                aldm_window_starts st, const int* __restrict__ phase_tab,
+                                                const int* __restrict__ step_idx, int rows, int B, int W, int C, int T, int Tw, int F,
+                                                int64_t total) {
+    typedef typename vec_of<V>::type vec;
+    const int phi = window_phase(phase_tab, step_idx, rows, T);
+    const int FV = F / V;
+    const int64_t wplane = (int64_t)Tw * F;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        int64_t q = i / FV;
+        const int fv = (int)(i - q * FV);
+        const int t = (int)(q % T);
+        q /= T;
+        const int c = (int)(q % C);
+        q /= C;
+        const int b = (int)(q % B);
+        const int64_t h = q / B;
+        vec acc = vec(0.0f);
+        bool first = true;
+        for (int j = 0; j < W; ++j) {
+            int p = t - phased_start(st.s[j], phi, T);
+            if (p < 0) p += T;
+            if (p >= Tw) continue;
+            const float wv = wn[(int64_t)j * Tw + p];
+            const vec e = *reinterpret_cast<const vec*>(win + ((((h * W + j) * B + b) * C + c) * wplane + (int64_t)p * F + fv * V));
+            if (first) {
+                acc = wv * e;
+                first = false;
+            } else if constexpr (V == 4) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) acc[k] = __builtin_fmaf(wv, e[k], acc[k]);
+            } else {
+                acc = __builtin_fmaf(wv, e, acc);
+            }
+        }
+        *reinterpret_cast<vec*>(out + i * V) = acc;
+    }
+}
+
+// window_blend_gather_ring_kernel with rotated starts: the blend is the sibling's (it does not depend on phi), then every window
+// copy of the owned element at its rotated, wrapped position.  A window position still maps to one frame and the rotated windows
+// still cover the circle: one writer per element of win, all written.
+template <int V>
+__global__ void window_blend_gather_ring_phased_kernel(float* __restrict__ x, const float* __restrict__ x0,
+                                                       const float* __restrict__ qnoise, const float* __restrict__ mask,
+                                                       const float* __restrict__ blend_coef, const int* __restrict__ step_idx,
+                                                       int q_rows, int coef_rows, float* __restrict__ win, aldm_window_starts st,
+                                                       const int* __restrict__ phase_tab, int rows, int B, int W, int C, int T, int Tw,
+                                                       int F, int64_t total) {
+    typedef typename vec_of<V>::type vec;
+    int s = step_idx ? *step_idx : 0;
+    s = s < 0 ? 0 : s;
+    const int qr = s < q_rows ? s : q_rows - 1, cr = s < coef_rows ? s : coef_rows - 1;
+    const float sa = blend_coef[2 * cr], so = blend_coef[2 * cr + 1];
+    const float* qn = qnoise + (int64_t)qr * total * V;
+    const int phi = window_phase(phase_tab, step_idx, rows, T);
+    const int FV = F / V;
+    const int64_t wplane = (int64_t)Tw * F;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        int64_t q = i / FV;
+        const int fv = (int)(i - q * FV);
+        const int t = (int)(q % T);
+        q /= T;
+        const int c = (int)(q % C);
+        const int64_t b = q / C;
+        const vec m = *reinterpret_cast<const vec*>(mask + i * V);
+        const vec orig = sa * *reinterpret_cast<const vec*>(x0 + i * V) + so * *reinterpret_cast<const vec*>(qn + i * V);
+        const vec v = orig * m + (1.0f - m) * *reinterpret_cast<const vec*>(x + i * V);
+        *reinterpret_cast<vec*>(x + i * V) = v;
+        for (int j = 0; j < W; ++j) {
+            int p = t - phased_start(st.s[j], phi, T);
             if (p < 0) p += T;
             if (p >= Tw) continue;
             *reinterpret_cast<vec*>(win + (((int64_t)j * B + b) * C + c) * wplane + (int64_t)p * F + fv * V) = v;
@@ -502,6 +624,92 @@ extern "C" int aldm_window_merge_ring(const float* win, const float* wn, float* 
                            B, W, C, T, Tw, F, n_out);
     }
     ALDM_LAUNCH_CHECK("aldm_window_merge_ring");
+    return 0;
+}
+
+// ---- the phased ring entries (ABI v25, moving window phases): the ring entries' checks, plus the phase table ----------------------
+// the table is `rows` int32: it may share no byte with a buffer the launch writes
+static inline bool phase_tab_overlaps(const int* tab, int rows, const float* buf, int64_t n) {
+    return spans_overlap(reinterpret_cast<const float*>(tab), rows, buf, n);
+}
+
+extern "C" int aldm_window_gather_ring_phased(const float* x, float* win, aldm_window_starts starts, const int* phase_tab,
+                                              const int* step_idx, int rows, int B, int W, int C, int T, int Tw, int F, void* stream) {
+    ALDM_CHECK(x && win, "aldm_window_gather_ring_phased: null pointer");
+    ALDM_CHECK(phase_tab, "aldm_window_gather_ring_phased: null phase table");
+    ALDM_CHECK(rows >= 1, "aldm_window_gather_ring_phased: rows=%d must be >= 1", rows);
+    if (window_ring_args_ok("aldm_window_gather_ring_phased", starts, B, W, C, T, Tw, F) != 0) return -1;
+    const int64_t n_x = (int64_t)B * C * T * F, n_w = (int64_t)W * B * C * Tw * F;
+    ALDM_CHECK(!spans_overlap(x, n_x, win, n_w), "aldm_window_gather_ring_phased: win overlaps x");
+    ALDM_CHECK(!phase_tab_overlaps(phase_tab, rows, win, n_w), "aldm_window_gather_ring_phased: win overlaps phase_tab");
+    const int64_t per_window = (int64_t)B * C * Tw * F;
+    const dim3 block(256);
+    if (F % 4 == 0 && (((uintptr_t)x | (uintptr_t)win) & 15) == 0) {
+        const dim3 grid(win_blocks(per_window / 4), W);
+        hipLaunchKernelGGL(window_gather_ring_phased_kernel<4>, grid, block, 0, (hipStream_t)stream, x, win, starts, phase_tab,
+                           step_idx, rows, T, Tw, F, (int64_t)Tw * F / 4, per_window / 4);
+    } else {
+        const dim3 grid(win_blocks(per_window), W);
+        hipLaunchKernelGGL(window_gather_ring_phased_kernel<1>, grid, block, 0, (hipStream_t)stream, x, win, starts, phase_tab,
+                           step_idx, rows, T, Tw, F, (int64_t)Tw * F, per_window);
+    }
+    ALDM_LAUNCH_CHECK("aldm_window_gather_ring_phased");
+    return 0;
+}
+
+extern "C" int aldm_window_blend_gather_ring_phased(float* x, const float* x0, const float* qnoise, const float* mask,
+                                                    const float* blend_coef, const int* step_idx, int q_rows, int coef_rows,
+                                                    float* win, aldm_window_starts starts, const int* phase_tab, int rows, int B,
+                                                    int W, int C, int T, int Tw, int F, void* stream) {
+    ALDM_CHECK(x && x0 && qnoise && mask && blend_coef && win, "aldm_window_blend_gather_ring_phased: null pointer");
+    ALDM_CHECK(phase_tab, "aldm_window_blend_gather_ring_phased: null phase table");
+    ALDM_CHECK(rows >= 1, "aldm_window_blend_gather_ring_phased: rows=%d must be >= 1", rows);
+    if (window_ring_args_ok("aldm_window_blend_gather_ring_phased", starts, B, W, C, T, Tw, F) != 0) return -1;
+    ALDM_CHECK(q_rows >= 1 && coef_rows >= 1, "aldm_window_blend_gather_ring_phased: q_rows=%d and coef_rows=%d must be >= 1", q_rows,
+               coef_rows);
+    const int64_t n_x = (int64_t)B * C * T * F, n_w = (int64_t)W * B * C * Tw * F, n_q = (int64_t)q_rows * n_x;
+    ALDM_CHECK(!spans_overlap(win, n_w, x, n_x) && !spans_overlap(win, n_w, x0, n_x) && !spans_overlap(win, n_w, qnoise, n_q) &&
+               !spans_overlap(win, n_w, mask, n_x), "aldm_window_blend_gather_ring_phased: win overlaps x, x0, qnoise or mask");
+    ALDM_CHECK(!spans_overlap(x, n_x, x0, n_x) && !spans_overlap(x, n_x, qnoise, n_q) && !spans_overlap(x, n_x, mask, n_x),
+               "aldm_window_blend_gather_ring_phased: x overlaps x0, qnoise or mask");
+    ALDM_CHECK(!phase_tab_overlaps(phase_tab, rows, win, n_w) && !phase_tab_overlaps(phase_tab, rows, x, n_x),
+               "aldm_window_blend_gather_ring_phased: win or x overlaps phase_tab");
+    const dim3 block(256);
+    if (F % 4 == 0 &&
+        (((uintptr_t)x | (uintptr_t)x0 | (uintptr_t)qnoise | (uintptr_t)mask | (uintptr_t)win) & 15) == 0) {
+        hipLaunchKernelGGL(window_blend_gather_ring_phased_kernel<4>, dim3(win_blocks(n_x / 4)), block, 0, (hipStream_t)stream, x, x0,
+                           qnoise, mask, blend_coef, step_idx, q_rows, coef_rows, win, starts, phase_tab, rows, B, W, C, T, Tw, F,
+                           n_x / 4);
+    } else {
+        hipLaunchKernelGGL(window_blend_gather_ring_phased_kernel<1>, dim3(win_blocks(n_x)), block, 0, (hipStream_t)stream, x, x0,
+                           qnoise, mask, blend_coef, step_idx, q_rows, coef_rows, win, starts, phase_tab, rows, B, W, C, T, Tw, F,
+                           n_x);
+    }
+    ALDM_LAUNCH_CHECK("aldm_window_blend_gather_ring_phased");
+    return 0;
+}
+
+extern "C" int aldm_window_merge_ring_phased(const float* win, const float* wn, float* out, aldm_window_starts starts,
+                                             const int* phase_tab, const int* step_idx, int rows, int H, int B, int W, int C, int T,
+                                             int Tw, int F, void* stream) {
+    ALDM_CHECK(win && wn && out, "aldm_window_merge_ring_phased: null pointer");
+    ALDM_CHECK(phase_tab, "aldm_window_merge_ring_phased: null phase table");
+    ALDM_CHECK(rows >= 1, "aldm_window_merge_ring_phased: rows=%d must be >= 1", rows);
+    ALDM_CHECK(H == 1 || H == 2, "aldm_window_merge_ring_phased: H=%d: 1, or 2 for the [uncond ; cond] pair", H);
+    if (window_ring_args_ok("aldm_window_merge_ring_phased", starts, B, W, C, T, Tw, F) != 0) return -1;
+    const int64_t n_out = (int64_t)H * B * C * T * F, n_w = (int64_t)H * W * B * C * Tw * F;
+    ALDM_CHECK(!spans_overlap(out, n_out, win, n_w) && !spans_overlap(out, n_out, wn, (int64_t)W * Tw),
+               "aldm_window_merge_ring_phased: out overlaps win or wn");
+    ALDM_CHECK(!phase_tab_overlaps(phase_tab, rows, out, n_out), "aldm_window_merge_ring_phased: out overlaps phase_tab");
+    const dim3 block(256);
+    if (F % 4 == 0 && (((uintptr_t)win | (uintptr_t)out) & 15) == 0) {
+        hipLaunchKernelGGL(window_merge_ring_phased_kernel<4>, dim3(win_blocks(n_out / 4)), block, 0, (hipStream_t)stream, win, wn, out,
+                           starts, phase_tab, step_idx, rows, B, W, C, T, Tw, F, n_out / 4);
+    } else {
+        hipLaunchKernelGGL(window_merge_ring_phased_kernel<1>, dim3(win_blocks(n_out)), block, 0, (hipStream_t)stream, win, wn, out,
+                           starts, phase_tab, step_idx, rows, B, W, C, T, Tw, F, n_out);
+    }
+    ALDM_LAUNCH_CHECK("aldm_window_merge_ring_phased");
     return 0;
 }
 

@@ -229,6 +229,10 @@ class DDIMSampler(SamplerBase):
                 # a row plan: the captured merge node reads the entry's weight buffer; this job's timeline goes INTO it (the key
                 # holds the row geometry only), outside any capture
                 ent["win"].wr.copy_(plan.win.wr)
+            if plan.win is not None and plan.win.phase is not None:
+                # a phased ring plan: the captured gather and merge nodes read the entry's phase table; this job's phases go INTO
+                # it (the key holds "phased" and the step count, not the values), outside any capture
+                ent["win"].phase.copy_(plan.win.phase)
         else:
             # static buffers = the graph's inputs
             ent = {"x_cur": img.clone(), "pred_x0": torch.empty_like(img), "t_cur": plan.t_tab[0].clone(),
@@ -243,6 +247,9 @@ class DDIMSampler(SamplerBase):
                 # the fused blend-and-gather node reads row step_idx of the q-noise table the feed fills
                 ent["qnoise_all"] = torch.empty_like(ent["noise_all"])
                 plan.win.qnoise, plan.win.step_idx = ent["qnoise_all"], ent["step_idx"]
+            if plan.win is not None and plan.win.phase is not None:
+                # moving window phases: the gather and merge nodes select the visit's phase with the graph's step counter
+                plan.win.step_idx = ent["step_idx"]
 
             def step(e=ent):
                 x_c = e["x_cur"]

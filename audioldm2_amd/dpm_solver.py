@@ -149,6 +149,9 @@ class DPMSolverSampler(SamplerBase):
             # fused blend-and-gather node reads it (q_rows = 1) and row step_idx of blend_coef
             qbuf = torch.empty_like(img)
             plan.win.qnoise, plan.win.step_idx = qbuf, step_idx
+        if plan.win is not None and plan.win.phase is not None:
+            # moving window phases: the gather and merge nodes select the step's phase with the counter
+            plan.win.step_idx = step_idx
 
         def step():
             eps = self.model_output(x_cur, t_cur, b, cond, unconditional_conditioning, use_cfg, prepared, win=plan.win)

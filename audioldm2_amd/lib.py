@@ -11,7 +11,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ALDM_LIB_PATH") or os.path.join(_HERE, "libaldm_hip.so")  # override: debug builds
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 ACT_NONE, ACT_SILU, ACT_LRELU, ACT_TANH, ACT_LOGCLAMP, ACT_GELU, ACT_GELU_TANH = range(7)
 B_PACKED, B_NT = 0, 1
@@ -209,6 +209,13 @@ _SIGS = {
     "aldm_window_blend_gather_ring": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                                 C.c_int, C.c_void_p, WindowStarts, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                 C.c_int, C.c_void_p]),
+    "aldm_window_gather_ring_phased": (C.c_int, [C.c_void_p, C.c_void_p, WindowStarts, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                                 C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "aldm_window_merge_ring_phased": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, WindowStarts, C.c_void_p, C.c_void_p, C.c_int,
+                                                C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "aldm_window_blend_gather_ring_phased": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                       C.c_int, C.c_int, C.c_void_p, WindowStarts, C.c_void_p, C.c_int, C.c_int,
+                                                       C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "aldm_window_gather_rows": (C.c_int, [C.c_void_p, C.c_void_p, WindowRows, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.c_void_p]),
     "aldm_window_merge_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, WindowRows, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,

@@ -1784,6 +1784,34 @@ def _window_entry(plan, name: str):
     return getattr(_l.load(), name + "_ring" if getattr(plan, "ring", False) else name)
 
 
+def _has_phase(plan) -> bool:
+    return getattr(plan, "phase", None) is not None
+
+
+def _window_phase(plan, phase: Optional[torch.Tensor], step_idx: Optional[torch.Tensor], what: str, device):
+    """The phase table of a phased ring plan's launch (windows.with_phase): `phase`, a contiguous int32 CUDA table
+    with one row per visit — None: plan.phase, uploaded once per plan and device — after checking it and the counter.  None for a
+    plan without a phase, which refuses `phase=`."""
+    if not _has_phase(plan):
+        if phase is not None:
+            raise RuntimeError(f"{what}.phase: the plan carries no phase (windows.with_phase)")
+        return None
+    if not getattr(plan, "ring", False) or _has_rows(plan):
+        raise RuntimeError(f"{what}: only a ring plan can carry a phase (windows.with_phase)")
+    if phase is None:
+        cache = plan.__dict__.setdefault("_phase_dev", {})
+        key = str(device)
+        if key not in cache:
+            cache[key] = plan.phase.to(device=device, dtype=torch.int32).contiguous()
+        phase = cache[key]
+    if not (torch.is_tensor(phase) and phase.is_cuda and phase.dtype == torch.int32 and phase.dim() == 1 and phase.numel() >= 1
+            and phase.is_contiguous()):
+        raise RuntimeError(f"{what}.phase: expected a contiguous 1-D int32 CUDA table with at least one row")
+    if step_idx is not None and (step_idx.dtype != torch.int32 or not step_idx.is_cuda or step_idx.numel() != 1):
+        raise RuntimeError(f"{what}.step_idx: expected one int32 on the device")
+    return phase
+
+
 def _no_overlap(out: torch.Tensor, what: str, others) -> None:
     a0, a1 = out.data_ptr(), out.data_ptr() + 4 * out.numel()
     for t, name in others:
@@ -1792,11 +1820,15 @@ def _no_overlap(out: torch.Tensor, what: str, others) -> None:
             raise RuntimeError(f"{what} overlaps {name}: the output must not alias an operand")
 
 
-def window_gather(x: torch.Tensor, plan, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+def window_gather(x: torch.Tensor, plan, out: Optional[torch.Tensor] = None, phase: Optional[torch.Tensor] = None,
+                  step_idx: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The windows of a long tensor (aldm_window_gather): x [B, C, T, F] -> [W*B, C, Tw, F], row j*B + b = x[b, :, s_j:s_j + Tw]
     (window-major), a bit-exact copy.  `plan`: windows.window_plan(T, Tw, hop); `out`: write into this (it may not overlap x).  A
     ring plan (plan.ring) takes aldm_window_gather_ring: row j*B + b = the frames (s_j + p) mod T, p in [0, Tw).  A row plan
-    (windows.row_plan) takes aldm_window_gather_rows: [R*B, C, Tw, F], row r*B + b = x[b, :, s_r:s_r + Tw] with the row starts s_r."""
+    (windows.row_plan) takes aldm_window_gather_rows: [R*B, C, Tw, F], row r*B + b = x[b, :, s_r:s_r + Tw] with the row starts s_r.
+    A phased ring plan (windows.with_phase) takes aldm_window_gather_ring_phased: the ring gather of x rolled by -phi along T, phi =
+    row `step_idx` (int32 [1] on the device, clamped into the table; None: row 0) of `phase` (a 1-D int32 device table; None: the
+    plan's own, uploaded once), clamped to [0, T - 1] on the device.  Every other plan ignores step_idx and refuses phase."""
     _chk(x, "window_gather.x")
     if x.dim() != 4 or x.shape[2] != plan.T or x.numel() == 0:
         raise RuntimeError(f"window_gather: x must be [B, C, T={plan.T}, F], got {tuple(x.shape)}")
@@ -1808,6 +1840,12 @@ def window_gather(x: torch.Tensor, plan, out: Optional[torch.Tensor] = None) -> 
     if tuple(out.shape) != shape:
         raise RuntimeError(f"window_gather.out: expected {shape}, got {tuple(out.shape)}")
     _no_overlap(out, "window_gather.out", [(x, "x")])
+    tab = _window_phase(plan, phase, step_idx, "window_gather", x.device)
+    if tab is not None:
+        _l.check(_l.load().aldm_window_gather_ring_phased(x.data_ptr(), out.data_ptr(), _window_starts(plan), tab.data_ptr(),
+                                                          _p(step_idx), tab.numel(), B, plan.W, C, T, plan.Tw, F, _stream()),
+                 "window_gather")
+        return out
     if _has_rows(plan):
         _l.check(_l.load().aldm_window_gather_rows(x.data_ptr(), out.data_ptr(), _window_rows(plan), B, C, T, plan.Tw, F, _stream()),
                  "window_gather")
@@ -1818,14 +1856,17 @@ def window_gather(x: torch.Tensor, plan, out: Optional[torch.Tensor] = None) -> 
 
 
 def window_blend_gather(x: torch.Tensor, x0: torch.Tensor, qnoise: torch.Tensor, mask: torch.Tensor, blend_coef: torch.Tensor, plan,
-                        step_idx: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                        step_idx: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                        phase: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The inpainting blend on a long latent and its window gather in one launch (aldm_window_blend_gather): in place
     x = (sa*x0 + so*qn)*mask + (1 - mask)*x, then the windows of the blended x -> [W*B, C, Tw, F] — bitwise inpaint_blend followed by
     window_gather.  x, x0, mask [B, C, T, F]; qnoise [q_rows, B, C, T, F], or [B, C, T, F] for one row; blend_coef [coef_rows, 2] =
     {sa, so}, or [2] for one row; step_idx (int32 [1] on the device, None: 0) selects row min(step_idx, rows - 1) of each table on
     the device.  `out`: write the windows into this.  out may overlap no operand, x none of x0, qnoise, mask.  A ring plan
     (plan.ring) takes aldm_window_blend_gather_ring: the same blend, the window copies at their wrapped positions.  A row plan
-    (windows.row_plan) takes aldm_window_blend_gather_rows: the same blend, a copy into every covering row."""
+    (windows.row_plan) takes aldm_window_blend_gather_rows: the same blend, a copy into every covering row.  A phased ring plan
+    (windows.with_phase) takes aldm_window_blend_gather_ring_phased: the same blend — x is left exactly as on the ring — and the
+    windows of the blended x rolled by -phi, phi = row step_idx of `phase` (see window_gather)."""
     for t, n in ((x, "x"), (x0, "x0"), (qnoise, "qnoise"), (mask, "mask"), (blend_coef, "blend_coef")):
         _chk(t, "window_blend_gather." + n)
     if x.dim() != 4 or x.shape[2] != plan.T or x.numel() == 0:
@@ -1855,6 +1896,13 @@ def window_blend_gather(x: torch.Tensor, x0: torch.Tensor, qnoise: torch.Tensor,
     others = [(x0, "x0"), (qnoise, "qnoise"), (mask, "mask")]
     _no_overlap(out, "window_blend_gather.out", [(x, "x")] + others + [(blend_coef, "blend_coef")])
     _no_overlap(x, "window_blend_gather.x", others + [(blend_coef, "blend_coef")])
+    tab = _window_phase(plan, phase, step_idx, "window_blend_gather", x.device)
+    if tab is not None:
+        _l.check(_l.load().aldm_window_blend_gather_ring_phased(x.data_ptr(), x0.data_ptr(), qnoise.data_ptr(), mask.data_ptr(),
+                                                                blend_coef.data_ptr(), _p(step_idx), q_rows, coef_rows,
+                                                                out.data_ptr(), _window_starts(plan), tab.data_ptr(), tab.numel(),
+                                                                B, plan.W, C, T, plan.Tw, F, _stream()), "window_blend_gather")
+        return out
     if _has_rows(plan):
         _l.check(_l.load().aldm_window_blend_gather_rows(x.data_ptr(), x0.data_ptr(), qnoise.data_ptr(), mask.data_ptr(),
                                                          blend_coef.data_ptr(), _p(step_idx), q_rows, coef_rows, out.data_ptr(),
@@ -1867,7 +1915,8 @@ def window_blend_gather(x: torch.Tensor, x0: torch.Tensor, qnoise: torch.Tensor,
     return out
 
 
-def window_merge(win: torch.Tensor, plan, out: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+def window_merge(win: torch.Tensor, plan, out: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None,
+                 phase: Optional[torch.Tensor] = None, step_idx: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The tapered, normalised overlap-add of window-wise tensors (aldm_window_merge): win [W*B, C, Tw, F] -> [B, C, T, F], or
     win [2, W*B, C, Tw, F] (the [uncond ; cond] pair of a guided UNet pass) -> [2, B, C, T, F]; rows window-major as
     window_gather writes them.  Per output element the covering windows in ascending order, wn*e first, then one fmaf each, in
@@ -1875,7 +1924,9 @@ def window_merge(win: torch.Tensor, plan, out: Optional[torch.Tensor] = None, we
     aldm_window_merge_ring: the overlap-add round the circle of plan.T frames.  A row plan (windows.row_plan, prompt timelines)
     takes aldm_window_merge_rows: win holds R*B rows, the weights are plan.wr [R, Tw], and a row whose weight at a frame is exactly 0
     is skipped there, its element not even loaded.  `weights` (a row plan only): read the [R, Tw] weights from this device tensor
-    instead of the plan's own upload — the static buffer of a cached step graph, refilled per job."""
+    instead of the plan's own upload — the static buffer of a cached step graph, refilled per job.  A phased ring plan
+    (windows.with_phase) takes aldm_window_merge_ring_phased: the ring merge's result rolled by +phi along T, bit for bit, phi = row
+    `step_idx` of `phase` (see window_gather); the weights are the ring plan's own, valid for every phase."""
     from .windows import device_weights
     _chk(win, "window_merge.win")
     W = _window_groups(plan)
@@ -1901,6 +1952,12 @@ def window_merge(win: torch.Tensor, plan, out: Optional[torch.Tensor] = None, we
             raise RuntimeError(f"window_merge.weights: expected {(W, plan.Tw)}, got {tuple(weights.shape)}")
         wn = weights
     _no_overlap(out, "window_merge.out", [(win, "win"), (wn, "wn")])
+    tab = _window_phase(plan, phase, step_idx, "window_merge", win.device)
+    if tab is not None:
+        _l.check(_l.load().aldm_window_merge_ring_phased(win.data_ptr(), wn.data_ptr(), out.data_ptr(), _window_starts(plan),
+                                                         tab.data_ptr(), _p(step_idx), tab.numel(), H, B, plan.W, C, plan.T, plan.Tw,
+                                                         F, _stream()), "window_merge")
+        return out
     if _has_rows(plan):
         _l.check(_l.load().aldm_window_merge_rows(win.data_ptr(), wn.data_ptr(), out.data_ptr(), _window_rows(plan), H, B, C, plan.T,
                                                   plan.Tw, F, _stream()), "window_merge")

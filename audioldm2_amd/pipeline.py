@@ -450,6 +450,38 @@ def check_resample_job(resample, ddim_steps, sampler, use_plms, ld):
     return check_resample(resample, len(make_ddim_timesteps("uniform", int(ddim_steps), int(ld.num_timesteps), verbose=False)))
 
 
+def phased_plan(plan, phase, loop, ddim_steps, ld, who):
+    """The `phase=` keyword of the long-form jobs (moving window phases), host only, before anything is drawn: None
+    -> `plan` itself; "golden" or a list of `ddim_steps` integers (latent frames) -> windows.with_phase(plan, table), the table one
+    entry per step of the run.  The run's step count is the length of the `ddim_steps` schedule (what check_resample_job counts):
+    the reference's uniform grid has one entry more than ddim_steps where ddim_steps does not divide the model's timesteps — "golden"
+    is evaluated over that length, a list's last phase is repeated for the extra step.  ValueError: phase without loop=True, an
+    unknown string, a list whose length is not ddim_steps or whose entries are not integers."""
+    if phase is None:
+        return plan
+    from .sampling import make_ddim_timesteps
+    from .windows import phase_table, with_phase
+    if not loop:
+        raise ValueError(f"{who}: phase= needs loop=True: moving window phases are a rotation of a ring's windows (a linear plan's "
+                         "gaps, and with them its normalisation, would change)")
+    if ddim_steps is None:
+        raise ValueError(f"{who}: phase= needs ddim_steps: the ancestral sampler has no windowed form")
+    if isinstance(phase, str):
+        if phase != "golden":
+            raise ValueError(f"{who}: unknown phase schedule {phase!r}: 'golden', or a list of one integer (latent frames) per step")
+    else:
+        try:
+            phase = list(phase)
+        except TypeError:
+            raise ValueError(f"{who}: phase must be 'golden' or a list of integers (latent frames), got {phase!r}")
+        if len(phase) != int(ddim_steps):
+            raise ValueError(f"{who}: {len(phase)} phases for ddim_steps={ddim_steps}: one per sampler step")
+    n = len(make_ddim_timesteps("uniform", int(ddim_steps), int(ld.num_timesteps), verbose=False))
+    if not isinstance(phase, str) and n > len(phase):
+        phase = phase + [phase[-1]] * (n - len(phase))
+    return with_phase(plan, phase_table(plan, n, phase))
+
+
 def _waveform_of(ld, samples, batch, text, n_gen, n_prompts, decision_shard=None):
     """The tail of a job: latent -> mel -> waveform, and with n_gen > 1 candidates per prompt (candidate-major, `n_prompts` rows per
     candidate) the one whose CLAP audio embedding is closest to the text's (ddpm.py:1554-1568, 1660-1670).  `decision_shard`
@@ -1163,7 +1195,7 @@ class LatentDiffusion(nn.Module):
     @torch.no_grad()
     def generate_batch_long(self, batch, latent_t_size, hop=None, ddim_steps=200, ddim_eta=1.0, unconditional_guidance_scale=1.0,
                             unconditional_conditioning=None, use_plms=False, sampler=None, negative_prompt=None,
-                            guidance_rescale=0.0, n_gen=1, shard=None, loop=False, boundaries=None, transition=0.0):
+                            guidance_rescale=0.0, n_gen=1, shard=None, loop=False, boundaries=None, transition=0.0, phase=None):
         """Long-form text-to-audio by windowed diffusion (MultiDiffusion, Bar-Tal et al. 2023): ONE long latent of
         `latent_t_size` frames; at every step the UNet runs on overlapping windows of `self.latent_t_size` frames — the trained
         length, `hop` frames apart (default 3*Tw//4) — in one pass over W*b rows, the windows' outputs are fused by a tapered,
@@ -1192,6 +1224,14 @@ class LatentDiffusion(nn.Module):
         hifigan.reach_frames(config) mel frames on both sides (one torch.cat per job), its output cut back to the clip.
         latent_t_size == the trained length is legal here (two half-shifted windows, one across the junction), hop == Tw is not.
 
+        `phase=` (with loop=True): moving window phases.  "golden", or a list of ddim_steps integers in latent
+        frames: at sampler step i every window start of the ring is rotated by phi_i frames, chosen on the device by the step
+        counter the replayed graph advances (the `_ring_phased` kernels), so no frame stays a window seam for the whole run.  The
+        ring's weights hold for every rotation and the UNet sees the same W*b rows.  The tail runs on the plan WITHOUT a phase: the
+        decode does not move.  No draw is added; phase=[0, ...] is the job without the keyword, bit for bit.  Refused before any
+        draw: phase without loop=True, an unknown string, a list whose length is not ddim_steps.  What moving phases do to the
+        sound of a trained model is not measured here.
+
         Refused before any draw or GPU work: ddim_steps=None (the ancestral sampler has no windowed form), n_gen != 1 (the CLAP
         re-ranker scores clips of the trained length), shard=, a length that is no multiple of 8 or shorter than the window, more
         than 32 windows; with loop=True also a hop of the whole window (no overlap: nothing would denoise across the junction);
@@ -1219,6 +1259,7 @@ class LatentDiffusion(nn.Module):
                                                        batch, ddim_steps)
         plan, mel_plan = self.long_form_plans(latent_t_size, hop, ring=loop)
         run_plan = plan if batches is None else _timeline_row_plan(plan, boundaries, transition)   # refuses, host only
+        run_plan = phased_plan(run_plan, phase, loop, ddim_steps, self, "generate_batch_long")   # refuses, host only; the tail: `plan`
         fb = batch["log_mel_spec"] if self.first_stage_key == "fbank" else batch[self.first_stage_key]
         B0 = fb.shape[0]
         f = 2 ** (self.first_stage_model.encoder.num_resolutions - 1)
@@ -1290,7 +1331,7 @@ class LatentDiffusion(nn.Module):
     def generate_batch_long_from_audio(self, batch, latent_t_size, keep, hop=None, ddim_steps=200, ddim_eta=1.0,
                                        unconditional_guidance_scale=1.0, use_plms=False, sampler=None, negative_prompt=None,
                                        guidance_rescale=0.0, n_gen=1, shard=None, loop=False, boundaries=None, transition=0.0,
-                                       feather=0, resample=None):
+                                       feather=0, phase=None, resample=None):
         """Continuation and inpainting of long clips: generate_batch_long around a source.  `batch["log_mel_spec"]`
         is the long mel [B0, latent_t_size*f, F_mel] of the source; `keep` lists the half-open latent-frame intervals [a, b) to
         keep (windows.keep_mask); everything else is generated under the prompt.  The source is encoded window by window
@@ -1324,8 +1365,12 @@ class LatentDiffusion(nn.Module):
         (aldm_keep_threshold_indexed) thresholds the level map into the binary mask the blend reads; the draws do not change, and
         timelines and `resample` work as before.  With every level 1 and feather == 0 the job is exactly the one without them.
 
+        `phase=` (with loop=True): moving window phases, as in generate_batch_long.  The source, the mask and the
+        level map live on the long latent in absolute frames and do not move: the blend is the ring's, only the window copies
+        change place (aldm_window_blend_gather_ring_phased).  With `resample` the phase follows the loop position of a visit.
+
         Refused before any draw or GPU work: ddim_steps=None, n_gen != 1, shard=, bad lengths or hops (long_form_plans), a bad
-        `keep` or `feather`, a mel whose length is not latent_t_size*f, a bad timeline (generate_batch_long), a bad `resample` (a malformed pair,
+        `phase` (generate_batch_long), a bad `keep` or `feather`, a mel whose length is not latent_t_size*f, a bad timeline (generate_batch_long), a bad `resample` (a malformed pair,
         n < 1, jump outside [1, steps - 1], together with use_plms=True or sampler="dpmpp_2m").
 
         Host-generator order (RNG contract R): (R1) randn(B0, C, latent_t_size, F) at the LONG shape, the
@@ -1350,6 +1395,8 @@ class LatentDiffusion(nn.Module):
         resample = check_resample_job(resample, ddim_steps, sampler, use_plms, self)
         plan, mel_plan = self.long_form_plans(latent_t_size, hop)
         ring_plans = self.long_form_plans(latent_t_size, hop, ring=True) if loop else None   # refuses a bad ring before any draw
+        # moving window phases ride on the ring plan of the sampling run only (refused here, before any draw, without loop=True)
+        ring_run = phased_plan(ring_plans[0] if loop else plan, phase, loop, ddim_steps, self, "generate_batch_long_from_audio")
         graded = _is_graded(keep, feather)
         mask_t = keep_levels(plan.T, keep, feather, ring=bool(loop)) if graded else keep_mask(plan.T, keep)
         # every level 1 and nothing feathered (a triple of level 1): exactly the call without levels
@@ -1369,7 +1416,7 @@ class LatentDiffusion(nn.Module):
         self.last_long_source = z
         if loop:   # the source was encoded on the linear plans; sampling and the tail run on the ring
             plan, mel_plan = ring_plans
-            run_plan = plan   # no timeline on a ring (_timeline_batches)
+            run_plan = ring_run   # no timeline on a ring (_timeline_batches); with phase= the phased ring, the tail stays on `plan`
         samples, _ = self.sample_log(cond=c, batch_size=B0, x_T=None, ddim=True, ddim_steps=ddim_steps, eta=ddim_eta,
                                      unconditional_guidance_scale=unconditional_guidance_scale,
                                      unconditional_conditioning=unconditional_conditioning, use_plms=use_plms,
@@ -1630,7 +1677,8 @@ def text_to_audio(latent_diffusion, text, transcription="", seed=42, ddim_steps=
 
 
 def text_to_audio_long(latent_diffusion, text, duration, overlap=2.5, transcription="", seed=42, ddim_steps=200, guidance_scale=3.5,
-                       sampler=None, negative_prompt=None, guidance_rescale=0.0, loop=False, timeline=None, transition=0.0):
+                       sampler=None, negative_prompt=None, guidance_rescale=0.0, loop=False, timeline=None, transition=0.0,
+                       phase=None):
     """Long-form text-to-audio: a clip of `duration` seconds — longer than the model's trained length — by windowed diffusion
     (LatentDiffusion.generate_batch_long): the UNet and the VAE work on windows of the model's `latent_t_size` frames that overlap
     by `overlap` seconds, fused at every step.  latent_t_size = int(duration * latent_t_per_second) must be a multiple of 8 and
@@ -1646,6 +1694,8 @@ def text_to_audio_long(latent_diffusion, text, duration, overlap=2.5, transcript
     Prompt k sounds from its start to the next one's, cross-faded over `transition` seconds round every start (0: hard cuts);
     seconds become latent frames by latent_t_per_second (timeline_frames).  A window that sees several prompts runs once under
     each, so the UNet pass grows from W to R rows (generate_batch_long).  Not together with loop=True.
+    `phase` (with loop=True; DESIGN.md §9k): moving window phases — "golden", or a list of ddim_steps integers in latent frames;
+    the ring's windows rotate from step to step so that no frame stays a window seam (generate_batch_long).
     Returns np.float32 [1, 1, samples]."""
     sampler_kw = _sampler_kwargs(sampler, negative_prompt, guidance_rescale)
     per_second = float(latent_diffusion.latent_t_per_second)
@@ -1653,7 +1703,10 @@ def text_to_audio_long(latent_diffusion, text, duration, overlap=2.5, transcript
     hop = latent_diffusion.latent_t_size - int(round(overlap * per_second))
     tl_kw, make = _timeline_entry(latent_diffusion, text, transcription, timeline, transition, loop, latent_t, hop, ddim_steps,
                                    "text_to_audio_long")
-    latent_diffusion.long_form_plans(latent_t, hop, ring=loop)   # refuse before any GPU work
+    ring = latent_diffusion.long_form_plans(latent_t, hop, ring=loop)[0]   # refuse before any GPU work
+    phased_plan(ring, phase, loop, ddim_steps, latent_diffusion, "text_to_audio_long")   # ... and before the seed is set
+    if phase is not None:
+        tl_kw = dict(tl_kw, phase=phase)
     seed_everything(int(seed))
     batch = make()
     with torch.no_grad():
@@ -1718,7 +1771,7 @@ def keep_frames(keep, per_second, latent_t):
 
 def extend_audio(latent_diffusion, text, original_audio_file_path, duration, keep=None, overlap=2.5, transcription="", seed=42,
                  ddim_steps=200, guidance_scale=3.5, sampler=None, negative_prompt=None, guidance_rescale=0.0, loop=False,
-                 timeline=None, transition=0.0, feather=0.0, resample=None):
+                 timeline=None, transition=0.0, feather=0.0, phase=None, resample=None):
     """Continue or inpaint a long clip: a clip of `duration` seconds — longer than the model's trained length — that keeps parts
     of the recording `original_audio_file_path` (a path, or a 1-D float waveform at 16 kHz; zero-padded or cut to `duration`) and
     generates the rest under the prompt `text` by windowed diffusion (LatentDiffusion.generate_batch_long_from_audio).  `keep`
@@ -1745,6 +1798,7 @@ def extend_audio(latent_diffusion, text, original_audio_file_path, duration, kee
     because the two round differently — in the context of its neighbours.  "Keep seconds 0-12, vary 12-15 only a little, make
     the rest new": keep=[(0, 12), (12, 15, 0.8)].  Vary a long recording, which audio_to_audio cannot: keep=[(0, 30, 0.5)].  One
     more small launch per step; pairs with feather 0 are exactly the job without levels.
+    `phase` (with loop=True): moving window phases, as in text_to_audio_long; the kept source does not move.
     Returns np.float32 [1, 1, samples]."""
     from .stft import TacotronSTFT
     from .windows import keep_levels, keep_mask
@@ -1758,11 +1812,13 @@ def extend_audio(latent_diffusion, text, original_audio_file_path, duration, kee
     per_second = float(latent_diffusion.latent_t_per_second)
     latent_t = int(duration * per_second)
     hop = latent_diffusion.latent_t_size - int(round(overlap * per_second))
-    latent_diffusion.long_form_plans(latent_t, hop)   # refuse before any GPU work
-    if loop:
-        latent_diffusion.long_form_plans(latent_t, hop, ring=True)
+    lin = latent_diffusion.long_form_plans(latent_t, hop)[0]   # refuse before any GPU work
+    ring = latent_diffusion.long_form_plans(latent_t, hop, ring=True)[0] if loop else lin
+    phased_plan(ring, phase, loop, ddim_steps, latent_diffusion, "extend_audio")
     tl_kw, make = _timeline_entry(latent_diffusion, text, transcription, timeline, transition, loop, latent_t, hop, ddim_steps,
                                    "extend_audio")
+    if phase is not None:
+        tl_kw = dict(tl_kw, phase=phase)
     f = 2 ** (latent_diffusion.first_stage_model.encoder.num_resolutions - 1)
     mel_bins = int(latent_diffusion.latent_f_size) * f
     if int(latent_diffusion.sampling_rate) != 16000 or mel_bins != 64:

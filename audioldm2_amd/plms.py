@@ -122,6 +122,10 @@ class PLMSSampler(SamplerBase):
             # fused blend-and-gather of the step's first pass reads it (q_rows = 1) and row step_idx of blend_coef
             qbuf = torch.empty_like(img)
             win.qnoise, win.step_idx = qbuf, step_idx
+        if win is not None and win.phase is not None:
+            # moving window phases: every pass's gather and merge select the step's phase with the counter (both passes of the
+            # eager step 0 run under row 0: the counter advances after them)
+            win.step_idx = step_idx
 
         def guided_eps(x, t_row, out=None, idx=None, first_pass=True):
             """eps [2, b, ...] for the step kernel to combine, or with rescale the combined and rescaled [b, ...] (row: the

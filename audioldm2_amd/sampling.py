@@ -514,7 +514,12 @@ class SamplerBase(object):
         R times — and the merge reads the per-row, per-frame weights from win.wr, a static [R, Tw] device buffer (eager passes into
         fresh tensors, `static=False`, read the same buffer).  plan_run is where a row plan and a PerPrompt are matched; here `cond` is
         normally its per-row result.  A PerPrompt that reaches this function is expanded with windows.rows_cond when win.plan has rows
-        and refused (ValueError) when it has none or the prompt counts differ; a row plan without win.wr / win.n == R is refused too."""
+        and refused (ValueError) when it has none or the prompt counts differ; a row plan without win.wr / win.n == R is refused too.
+
+        A phased ring plan (windows.with_phase, moving window phases): the same three launches in their `_ring_phased`
+        forms.  All of a pass's launches read the phase of the visit from win.phase — a static int32 device table, one row per visit
+        — with the device-side counter win.step_idx, so gather and merge of one pass agree and a replayed step graph moves its
+        windows without the host.  The sampler sets win.step_idx before its first step; None reads row 0."""
         from .windows import PerPrompt, has_rows, rows_cond
         rows = win is not None and has_rows(win.plan)
         if isinstance(cond, PerPrompt):
@@ -526,6 +531,9 @@ class SamplerBase(object):
             raise ValueError("model_output: a row plan needs win.n == plan.R and win.wr, the [R, Tw] merge weights on the device "
                              "(plan_run builds both)")
         if win is not None:
+            phase = getattr(win, "phase", None)
+            # moving window phases: gather and merge read the same row of the same table with the same counter
+            phased = {} if phase is None else {"phase": phase, "step_idx": win.step_idx}
             if win.blend and first_pass:
                 # a plan with a source: the blend of the known region on the long latent, in place, and the gather are one launch
                 if getattr(win, "level", None) is not None:
@@ -533,11 +541,11 @@ class SamplerBase(object):
                     # blend, reading the same counter — a node of the captured step like the blend itself
                     ops.keep_threshold_indexed(win.level, win.keep_thr, win.mask, win.step_idx)
                 xw = ops.window_blend_gather(x, win.x0, win.qnoise, win.mask, win.blend_coef, win.plan, step_idx=win.step_idx,
-                                             out=win.xw if static else None)
+                                             out=win.xw if static else None, phase=phase)
             else:
-                xw = ops.window_gather(x, win.plan, out=win.xw if static else None)
+                xw = ops.window_gather(x, win.plan, out=win.xw if static else None, **phased)
             eps_w = self.model_output(xw, t_row, win.n * b, cond, uncond, use_cfg, prepared)
-            return ops.window_merge(eps_w.contiguous(), win.plan, out=win.merged if static else None, weights=win.wr)
+            return ops.window_merge(eps_w.contiguous(), win.plan, out=win.merged if static else None, weights=win.wr, **phased)
         if not use_cfg:
             return self.model.apply_model(x, t_row[:b].long(), cond).contiguous()
         if hasattr(self.model, "apply_model_cfg"):
@@ -581,12 +589,18 @@ class SamplerBase(object):
         Refused (ValueError) before the first draw: no mask or source, levels that are not finite or leave [0, 1].  Without it
         p.level_d and p.keep_thr are None and nothing changes.
 
+        A phased ring plan (windows.with_phase): its table must have one entry per step of the cut schedule —
+        `total_steps`; ValueError before the first draw otherwise — and p.win.phase holds it on the device as int32 with one row per
+        VISIT: a step visit at loop position i has entry i, a renoise visit (not read) the next step visit's, blend_coef's rule.
+        The samplers point p.win.step_idx at their step counter.  No draw is added; without a phase p.win.phase is None.
+
         RNG contract R: x_T is the host generator's first draw of the run, made only when x_T is not given; `draw` makes the
         loop's later ones.  A start latent that already lives on the device (audio-to-audio) stays there.  Host -> device copies,
-        in this order: img, coef, t_tab, mask_d, x0_d, blend_coef, keep_thr, then the model's prepare_cfg."""
+        in this order: img, coef, t_tab, mask_d, x0_d, blend_coef, keep_thr, (a row plan's wr, a phased plan's phase,) then the
+        model's prepare_cfg."""
         dev = torch.device("cuda")
         shape = tuple(shape)
-        from .windows import check_per_prompt, has_rows
+        from .windows import check_per_prompt, has_phase, has_rows
         check_per_prompt(cond, windows)   # a row plan and a PerPrompt conditioning go together, or neither
         W, source = 1, None
         if windows is not None:
@@ -622,6 +636,10 @@ class SamplerBase(object):
                 raise ValueError("resample=: the cut schedule has no step to run")
             if check_resample(resample, total_steps)[0] > 1:
                 p.visits = resample_visits(total_steps, *resample)
+        phased = windows is not None and has_phase(windows)
+        if phased and int(windows.phase.numel()) != total_steps:
+            raise ValueError(f"windows=: the plan's phase table has {int(windows.phase.numel())} entries, the run {total_steps} "
+                             "steps: one phase per sampler step (windows.phase_table over the cut schedule)")
         p.time_range = np.flip(ts).copy()   # own storage, positive strides: from_numpy refuses the flipped view, even of one entry
         # guidance rescale: the combine and the per-sample rescale run in a launch of their own in front of the step kernel
         p.rescale = use_cfg and guidance_rescale > 0.0
@@ -668,7 +686,13 @@ class SamplerBase(object):
                                     step_idx=None, n=W, level=p.level_d, keep_thr=p.keep_thr,
                                     # a row plan: the merge's [R, Tw] weights, a static buffer of the run (of the step graph's
                                     # cache entry, which refills it per job: two timelines of one row geometry share a graph)
-                                    wr=windows.wr.to(dev).contiguous() if has_rows(windows) else None)
+                                    wr=windows.wr.to(dev).contiguous() if has_rows(windows) else None, phase=None)
+            if phased:
+                # moving window phases: one int32 row per visit, selected on the device by the sampler's step counter — a static
+                # buffer of the run (of the step graph's cache entry, which refills it per job, as it refills wr)
+                pos = torch.arange(total_steps) if p.visits is None else \
+                    torch.tensor([v[1] if v[0] == "step" else v[2] for v in p.visits], dtype=torch.long)
+                p.win.phase = windows.phase.to(torch.int32)[pos].contiguous().to(dev)
         if use_cfg and hasattr(self.model, "apply_model_cfg") and hasattr(self.model, "prepare_cfg"):
             p.prepared = self.model.prepare_cfg(p.cond, p.uncond)
         return p

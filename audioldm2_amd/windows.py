@@ -12,6 +12,9 @@ may be a map of keep LEVELS (`keep_levels`, `with_source(..., graded=True)`; DES
 A linear plan may carry a prompt timeline (`prompt_weights`, `row_plan`, `PerPrompt`, `rows_cond`): every prompt has a
 weight per latent frame, a window that sees several prompts becomes one ROW per prompt, the UNet runs on the rows — each under its
 own prompt's conditioning — and the rows are fused per frame by taper times prompt weight (the `_rows` forms of the three launches).
+
+A ring plan may carry moving window phases (`phase_table`, `with_phase`): at every sampler step all starts of the ring
+are rotated by that step's phase, chosen on the device by the samplers' step counter (the `_ring_phased` forms of the three launches).
 """
 from __future__ import annotations
 
@@ -125,7 +128,87 @@ def plan_key(plan):
     part of the key: they live in a static buffer of the step graph's cache entry, refilled per job."""
     if has_rows(plan):
         return (plan.T, plan.Tw, tuple(plan.row_starts), "rows")
+    if has_phase(plan):
+        # moving window phases (with_phase): the phased ring kernels, distinct from every linear, ring and row key.  The table's
+        # VALUES are not part of the key: they live in a static buffer of the step graph's cache entry, refilled per job
+        return (plan.T, plan.Tw, tuple(plan.starts), "phased")
     return (plan.T, plan.Tw, tuple(plan.starts), bool(getattr(plan, "ring", False)))
+
+
+# ---- moving window phases (DESIGN.md §9k): a ring's starts rotated by a per-step phase ------------------------------------------------
+GOLDEN = 0.6180339887498949   # frac of the golden ratio: the additive recurrence with the lowest discrepancy
+
+
+def has_phase(plan):
+    """True for a ring plan that carries a phase table (with_phase): its launches are the `_ring_phased` kernels."""
+    return getattr(plan, "phase", None) is not None
+
+
+def ring_gap(plan):
+    """The largest gap between a ring plan's starts, the wrap gap T - s_{W-1} included."""
+    if not getattr(plan, "ring", False):
+        raise ValueError("ring_gap: not a ring plan (window_plan(..., ring=True))")
+    s = list(plan.starts)
+    return max(b - a for a, b in zip(s, s[1:] + [plan.T]))
+
+
+def phase_table(plan, steps, phase="golden"):
+    """The per-step window phases of a ring plan -> int32 [steps] (host): at sampler step i every window start is rotated by
+    phi_i frames, window j covering the frames (s_j + phi_i + p) mod T.
+
+      phase="golden"   phi_i = floor(frac(i * 0.6180339887498949) * G) in fp64, G = ring_gap(plan): phi_0 = 0, every value in
+                       [0, G) — a rotation by a whole gap maps an equal-gap ring onto itself — and neighbouring steps far apart.
+                       Deterministic: no draw from any generator.
+      phase=[...]      one integer (latent frames) per sampler step, reduced mod T here; the length must be `steps`.
+
+    ValueError: a plan that is not a ring or has rows, steps not a positive integer, an unknown string, entries that are not
+    integers, a wrong length."""
+    if not getattr(plan, "ring", False) or has_rows(plan):
+        raise ValueError("phase_table: moving window phases need a ring plan (window_plan(..., ring=True)): a rotation changes a "
+                         "linear plan's gaps and with them its normalisation")
+    if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or steps < 1:
+        raise ValueError(f"phase_table: steps must be a positive integer, got {steps!r}")
+    steps = int(steps)
+    if isinstance(phase, str):
+        if phase != "golden":
+            raise ValueError(f"phase_table: unknown phase schedule {phase!r}: 'golden', or a list of one integer per step")
+        x = np.arange(steps, dtype=np.float64) * GOLDEN
+        vals = np.floor((x - np.floor(x)) * float(ring_gap(plan))).astype(np.int64)
+    else:
+        try:
+            seq = list(phase)
+        except TypeError:
+            raise ValueError(f"phase_table: phase must be 'golden' or a sequence of integers (latent frames), got {phase!r}")
+        for v in seq:
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"phase_table: a phase must be an integer number of latent frames, got {v!r}")
+        if len(seq) != steps:
+            raise ValueError(f"phase_table: {len(seq)} phases for a run of {steps} steps: one per sampler step")
+        vals = np.asarray([int(v) % plan.T for v in seq], dtype=np.int64)
+    return torch.from_numpy(vals.astype(np.int32))
+
+
+def with_phase(plan, table):
+    """`plan` with moving window phases: a copy of the ring plan that carries `phase`, the int32 [steps] table of
+    phase_table — one entry per sampler step of the run it is given to, reduced mod T here (the kernels clamp, they do not wrap).
+    Same T, Tw, starts and wn; the plan_key becomes (T, Tw, starts, "phased").  Composes with with_source in either order.
+    ValueError: a plan that is not a ring, a row plan, a table that is not a 1-D integer tensor (or sequence), a length of 0."""
+    if has_rows(plan):
+        raise ValueError("with_phase: a row plan (a prompt timeline) cannot carry a phase: row plans are linear")
+    if not getattr(plan, "ring", False):
+        raise ValueError("with_phase: moving window phases need a ring plan (window_plan(..., ring=True)): a rotation changes a "
+                         "linear plan's gaps and with them its normalisation")
+    if not torch.is_tensor(table):
+        try:
+            table = torch.as_tensor(np.asarray(table))
+        except (TypeError, ValueError, RuntimeError):
+            raise ValueError(f"with_phase: the table must be a 1-D integer tensor, got {type(table).__name__}")
+    if table.dim() != 1 or table.dtype not in (torch.int32, torch.int64, torch.int16, torch.int8, torch.uint8):
+        raise ValueError(f"with_phase: the table must be a 1-D integer tensor, got {table.dtype} {tuple(table.shape)}")
+    if table.numel() == 0:
+        raise ValueError("with_phase: the table is empty: one phase per sampler step")
+    table = torch.remainder(table.detach().cpu().to(torch.int64), plan.T).to(torch.int32).contiguous()
+    return SimpleNamespace(**dict(plan.__dict__, phase=table))
 
 
 # ---- prompt timelines (DESIGN.md §9h): per-frame prompt weights, rows = (window, prompt) pairs -----------------------------------------

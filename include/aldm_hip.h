@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 /* ---- library / error ------------------------------------------------------------------ */
-int aldm_version(void);              /* ABI version (24),bumped on any struct / entry change */
+int aldm_version(void);              /* ABI version (25),bumped on any struct / entry change */
 const char* aldm_last_error(void);   /* message of the last failing call on this thread     */
 
 /* ---- activations usable as prologue (applied to the gathered input) or epilogue -------- */
@@ -661,6 +661,28 @@ int aldm_window_merge_ring(const float* win, const float* wn, float* out, aldm_w
 int aldm_window_blend_gather_ring(float* x, const float* x0, const float* qnoise, const float* mask, const float* blend_coef,
                                   const int* step_idx, int q_rows, int coef_rows, float* win, aldm_window_starts starts, int B,
                                   int W, int C, int T, int Tw, int F, void* stream);
+/* Moving window phases, ABI v25: a ring plan whose starts are all rotated, per step, by a phase the device-side step
+ * counter selects — window j covers the frames (s_j + phi + p) mod T, p in [0, Tw).  A rigid rotation keeps every gap, so the ring
+ * plan's weights wn hold for every phase.  The three entries below are siblings of the ring entries, which are unchanged.
+ * `starts`: the ring plan's own, by value, checked on the host exactly as the ring entries check them.  `phase_tab`: a device table
+ * of `rows` int32.  Row r = clamp(step_idx ? *step_idx : 0, 0, rows - 1) (aldm_keep_threshold_indexed's conventions; the counter is
+ * read, never written) and phi = clamp(phase_tab[r], 0, T - 1): a value outside [0, T) CLAMPS, it does not wrap — whatever the table
+ * holds, the launch stays inside its buffers; a caller reduces mod T on the host.  Host checks before every launch: the ring
+ * entries' own, phase_tab != NULL, rows >= 1, the siblings' overlap rules, and phase_tab overlapping no written buffer.  With
+ * phi == 0 each entry is bitwise its ring sibling.  16-byte accesses along F under the siblings' alignment rule.                   */
+/* win == aldm_window_gather_ring of x rolled by -phi along T: win[(j*B + b), c, p, f] = x[b, c, (s_j + phi + p) mod T, f]. */
+int aldm_window_gather_ring_phased(const float* x, float* win, aldm_window_starts starts, const int* phase_tab, const int* step_idx,
+                                   int rows, int B, int W, int C, int T, int Tw, int F, void* stream);
+/* out == aldm_window_merge_ring's result rolled by +phi along T, bit for bit: per output element the covering windows in ascending
+ * j, the first term a plain multiply, every later one one fmaf; H = 1 | 2; gather form, no atomics.                               */
+int aldm_window_merge_ring_phased(const float* win, const float* wn, float* out, aldm_window_starts starts, const int* phase_tab,
+                                  const int* step_idx, int rows, int H, int B, int W, int C, int T, int Tw, int F, void* stream);
+/* aldm_window_blend_gather_ring with rotated windows: x is left exactly as the ring sibling leaves it (the blend does not depend on
+ * phi; step_idx selects the q-noise and coefficient rows as there, and the phase row), win == aldm_window_gather_ring of the blended
+ * x rolled by -phi.  Every window element has exactly one writer and all are written; no atomics.                                 */
+int aldm_window_blend_gather_ring_phased(float* x, const float* x0, const float* qnoise, const float* mask, const float* blend_coef,
+                                         const int* step_idx, int q_rows, int coef_rows, float* win, aldm_window_starts starts,
+                                         const int* phase_tab, int rows, int B, int W, int C, int T, int Tw, int F, void* stream);
 /* Prompt timelines, ABI v22: a ROW is one window under one prompt, so several rows may share a start.  The row starts
  * travel by value like the window starts; 64 of them (a two-minute clip with a scene every 10 s takes 35).  The three entries below
  * are siblings of aldm_window_gather, aldm_window_merge and aldm_window_blend_gather; those are unchanged and keep refusing repeated
