@@ -259,6 +259,72 @@ __global__ void dpmpp_step_indexed_vec4_kernel(float* __restrict__ x, const floa
     }
 }
 
+// ---- DPM-Solver++(2M) SDE (Lu et al. 2022, the SDE variant in its midpoint form; eta from the ODE solver to the full SDE) -------
+// The same row, with c2 = (sigma_prev / sigma_t) exp(-eta h), c3 = -alpha_prev expm1(-(1 + eta) h) and, in column 8,
+// c4 = sigma_prev sqrt(-expm1(-2 eta h)):  dpmpp_elem's expression and order, then  x = (c2 x + c3 D) + c4 z,  z the step's unit
+// noise: row clamp(*step_idx, 0, noise_rows - 1) of noise_tab [noise_rows, n] — the blend kernels' clamp, so the launch stays inside
+// the table whatever the counter holds.  The product c4 z and the sum are rounded separately (no contraction).  With c4 == 0 the noise
+// element is not even loaded: a NaN table cannot reach x and the launch is bitwise dpmpp_step_indexed_kernel's.
+__device__ __forceinline__ int64_t dpmpp_sde_noise_row(const int* __restrict__ step_idx, int noise_rows) {
+    const int s = *step_idx;
+    return s < 0 ? 0 : (s > noise_rows - 1 ? noise_rows - 1 : s);
+}
+
+__global__ void dpmpp_sde_step_indexed_kernel(float* __restrict__ x, const float* __restrict__ eps, float* __restrict__ x0_buf,
+                                              const float* __restrict__ noise_tab, int noise_rows,
+                                              const float* __restrict__ coef_tab, const int* __restrict__ step_idx, int64_t n,
+                                              int coef_ld) {
+    const dpmpp_row r = dpmpp_load_row(coef_tab, step_idx, coef_ld);
+    const float c4 = coef_tab[(int64_t)*step_idx * coef_ld + 8];
+    const bool noisy = c4 != 0.f;
+    const float* noise = noise_tab + dpmpp_sde_noise_row(step_idx, noise_rows) * n;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        float xv = x[i], p0;
+        dpmpp_elem(r, xv, eps[i], r.cfg ? eps[n + i] : 0.f, r.second ? x0_buf[i] : 0.f, p0);
+        if (noisy) {
+            const float nz = c4 * noise[i];
+            xv = xv + nz;
+        }
+        x[i] = xv;
+        x0_buf[i] = p0;
+    }
+}
+
+// the same with 16 bytes per lane and access: n4 = n / 4 for n % 4 == 0 and 16-byte aligned operands (so is every noise row then)
+__global__ void dpmpp_sde_step_indexed_vec4_kernel(float* __restrict__ x, const float* __restrict__ eps,
+                                                   float* __restrict__ x0_buf, const float* __restrict__ noise_tab, int noise_rows,
+                                                   const float* __restrict__ coef_tab, const int* __restrict__ step_idx, int64_t n4,
+                                                   int coef_ld) {
+    const dpmpp_row r = dpmpp_load_row(coef_tab, step_idx, coef_ld);
+    const float c4 = coef_tab[(int64_t)*step_idx * coef_ld + 8];
+    const bool noisy = c4 != 0.f;
+    f32x4* xq = reinterpret_cast<f32x4*>(x);
+    f32x4* hq = reinterpret_cast<f32x4*>(x0_buf);
+    const f32x4* eq = reinterpret_cast<const f32x4*>(eps);
+    const f32x4* nq = reinterpret_cast<const f32x4*>(noise_tab) + dpmpp_sde_noise_row(step_idx, noise_rows) * n4;
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+        f32x4 xv = xq[i], p0;
+        const f32x4 eu = eq[i];
+        const f32x4 ec = r.cfg ? eq[n4 + i] : zero;
+        const f32x4 old = r.second ? hq[i] : zero;
+        const f32x4 nv = noisy ? nq[i] : zero;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float xk = xv[k], pk;
+            dpmpp_elem(r, xk, eu[k], ec[k], old[k], pk);
+            if (noisy) {
+                const float nz = c4 * nv[k];
+                xk = xk + nz;
+            }
+            xv[k] = xk;
+            p0[k] = pk;
+        }
+        xq[i] = xv;
+        hq[i] = p0;
+    }
+}
+
 // ---- guidance rescale (Lin et al. 2023, "Common Diffusion Noise Schedules and Sample Steps are Flawed", section 3.4) -------------
 // Row s = *step_idx (row 0 without a counter) of coef_tab: column 5 = guidance scale, column 7 = phi.  Per sample b of eps[2, B, n_s]:
 //   e_g = e_u + s (e_c - e_u);  f = phi std(e_c) / std(e_g) + (1 - phi);  out = f e_g      (f = 1 when std(e_g) == 0 or n_s == 1)
@@ -545,6 +611,28 @@ extern "C" int aldm_dpmpp_step_indexed(float* x, const float* eps, float* x0_buf
         hipLaunchKernelGGL(dpmpp_step_indexed_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, x, eps, x0_buf,
                            coef_tab, step_idx, n, coef_ld);
     ALDM_LAUNCH_CHECK("aldm_dpmpp_step_indexed");
+    return 0;
+}
+
+extern "C" int aldm_dpmpp_sde_step_indexed(float* x, const float* eps, float* x0_buf, const float* noise_tab, int noise_rows,
+                                           const float* coef_tab, const int* step_idx, int64_t n, int coef_ld, void* stream) {
+    ALDM_CHECK(x && eps && x0_buf && noise_tab && coef_tab && step_idx, "aldm_dpmpp_sde_step_indexed: null pointer");
+    ALDM_CHECK(n > 0 && noise_rows >= 1 && coef_ld >= 9,
+               "aldm_dpmpp_sde_step_indexed: bad args (n=%lld, noise_rows=%d, coef_ld=%d: rows of >= 9 floats)", (long long)n,
+               noise_rows, coef_ld);
+    // both in-place operands against the whole table: a step writes them while it reads its noise row
+    const uintptr_t t0 = (uintptr_t)noise_tab, t1 = t0 + (uintptr_t)noise_rows * (uintptr_t)n * sizeof(float);
+    const uintptr_t nb = (uintptr_t)n * sizeof(float);
+    ALDM_CHECK((uintptr_t)x + nb <= t0 || t1 <= (uintptr_t)x, "aldm_dpmpp_sde_step_indexed: x overlaps noise_tab");
+    ALDM_CHECK((uintptr_t)x0_buf + nb <= t0 || t1 <= (uintptr_t)x0_buf, "aldm_dpmpp_sde_step_indexed: x0_buf overlaps noise_tab");
+    const bool vec = n % 4 == 0 && (((uintptr_t)x | (uintptr_t)eps | (uintptr_t)x0_buf | (uintptr_t)noise_tab) & 15) == 0;
+    if (vec)
+        hipLaunchKernelGGL(dpmpp_sde_step_indexed_vec4_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, x, eps,
+                           x0_buf, noise_tab, noise_rows, coef_tab, step_idx, n / 4, coef_ld);
+    else
+        hipLaunchKernelGGL(dpmpp_sde_step_indexed_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, x, eps, x0_buf,
+                           noise_tab, noise_rows, coef_tab, step_idx, n, coef_ld);
+    ALDM_LAUNCH_CHECK("aldm_dpmpp_sde_step_indexed");
     return 0;
 }
 

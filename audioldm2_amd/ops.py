@@ -1600,6 +1600,27 @@ def dpmpp_step_indexed(x: torch.Tensor, eps: torch.Tensor, x0_buf: torch.Tensor,
     return x
 
 
+def dpmpp_sde_step_indexed(x: torch.Tensor, eps: torch.Tensor, x0_buf: torch.Tensor, noise: torch.Tensor, coef: torch.Tensor,
+                           step_idx: torch.Tensor) -> torch.Tensor:
+    """A DPM-Solver++(2M) SDE step in place on x (aldm_dpmpp_sde_step_indexed): ops.dpmpp_step_indexed's operands and
+    row — columns 0-7 of coef [S, >= 9] are what it reads — then x += c4 z with c4 = the row's column 8 and z the row of `noise`
+    [V, *x.shape] (or one row [*x.shape]) the int32 device counter `step_idx` selects, clamped into the table.  A row with c4 == 0
+    does not load its noise and is bitwise ops.dpmpp_step_indexed.  x and x0_buf may share no byte with the noise table."""
+    for t, n in ((x, "x"), (eps, "eps"), (x0_buf, "x0_buf"), (noise, "noise"), (coef, "coef")):
+        _chk(t, "dpmpp_sde_indexed." + n)
+    assert step_idx.dtype == torch.int32 and step_idx.is_cuda and coef.dim() == 2
+    assert x0_buf.shape == x.shape and eps.numel() in (x.numel(), 2 * x.numel())
+    if x.numel() == 0 or tuple(noise.shape) not in (tuple(x.shape), tuple(noise.shape[:1]) + tuple(x.shape)):
+        raise RuntimeError(f"dpmpp_sde_indexed.noise: expected {tuple(x.shape)} or [V, {', '.join(str(d) for d in x.shape)}], got "
+                           f"{tuple(noise.shape)}")
+    _no_overlap(x, "dpmpp_sde_indexed.x", [(noise, "noise")])
+    _no_overlap(x0_buf, "dpmpp_sde_indexed.x0_buf", [(noise, "noise")])
+    _l.check(_l.load().aldm_dpmpp_sde_step_indexed(x.data_ptr(), eps.data_ptr(), x0_buf.data_ptr(), noise.data_ptr(),
+                                                   noise.numel() // x.numel(), coef.data_ptr(), step_idx.data_ptr(), x.numel(),
+                                                   coef.shape[1], _stream()), "dpmpp_sde_step_indexed")
+    return x
+
+
 def cfg_rescale_indexed(eps: torch.Tensor, out: torch.Tensor, coef: torch.Tensor,
                         step_idx: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The guidance combine with guidance rescale (aldm_cfg_rescale_indexed; Lin et al. 2023, section 3.4): per sample b of

@@ -274,7 +274,7 @@ class DiffusionWrapper(nn.Module):
                                     context_attn_mask_list=masks)
 
 
-SAMPLERS = ("dpmpp_2m",)   # what `sampler=` names besides the reference's own choices (DDIM, use_plms=True, ancestral)
+SAMPLERS = ("dpmpp_2m", "dpmpp_2m_sde")   # what `sampler=` names besides the reference's own choices (DDIM, use_plms=True, ancestral)
 
 
 def _timeline_batches(batch, boundaries, loop, who):
@@ -738,7 +738,8 @@ class LatentDiffusion(nn.Module):
     @torch.no_grad()
     def sample_log(self, cond, batch_size, ddim, ddim_steps, unconditional_guidance_scale=1.0,
                    unconditional_conditioning=None, use_plms=False, mask=None, **kwargs):
-        """ddpm.py:1418-1474; `sampler="dpmpp_2m"` (a keyword of **kwargs, no reference counterpart) runs DPMSolverSampler."""
+        """ddpm.py:1418-1474; `sampler="dpmpp_2m"` (a keyword of **kwargs, no reference counterpart) runs DPMSolverSampler,
+        `sampler="dpmpp_2m_sde"` DPMSolverSDESampler."""
         sampler_name = resolve_sampler(kwargs.pop("sampler", None), use_plms)
         # `guidance_rescale` (phi of Lin et al. 2023, a keyword of **kwargs too) goes to whichever of the three samplers runs
         from .sampling import check_guidance_rescale
@@ -808,6 +809,13 @@ class LatentDiffusion(nn.Module):
                 raise ValueError("sampler='dpmpp_2m' needs ddim_steps")
             from . import dpm_solver
             sampler = dpm_solver.DPMSolverSampler(self)
+        elif sampler_name == "dpmpp_2m_sde":
+            # the stochastic member of the family: eta travels on; outside (0, 1] it raises in
+            # DPMSolverSDESampler.make_schedule
+            if ddim_steps is None:
+                raise ValueError("sampler='dpmpp_2m_sde' needs ddim_steps")
+            from . import dpm_solver
+            sampler = dpm_solver.DPMSolverSDESampler(self)
         elif ddim:
             sampler = DDIMSampler(self, device=self.device)
         else:
@@ -1538,10 +1546,10 @@ def wav_to_fbank(source, target_length=1024, fn_STFT=None):
 
 
 def _sampler_kwargs(sampler, negative_prompt=None, guidance_rescale=0.0):
-    """What the two entry points add to generate_batch* for `sampler=`: nothing for None (today's call, unchanged); a named
-    sampler is deterministic, and these entry points have no eta parameter, so eta 0 goes with the name.  `negative_prompt` and
-    `guidance_rescale` travel the same way, and only when set."""
-    kw = {} if resolve_sampler(sampler) is None else {"sampler": sampler, "ddim_eta": 0.0}
+    """What the entry points add to generate_batch* for `sampler=`: nothing for None (today's call, unchanged).  These entry points
+    have no eta parameter, so eta goes with the name: 0 with the deterministic "dpmpp_2m", 1 — the full SDE, the reference's own
+    amount of noise — with "dpmpp_2m_sde".  `negative_prompt` and `guidance_rescale` travel the same way, and only when set."""
+    kw = {} if resolve_sampler(sampler) is None else {"sampler": sampler, "ddim_eta": 1.0 if sampler == "dpmpp_2m_sde" else 0.0}
     if negative_prompt is not None:
         kw["negative_prompt"] = negative_prompt
     if guidance_rescale != 0.0:
@@ -1556,7 +1564,8 @@ def super_resolution_and_inpainting(latent_diffusion, text, transcription="", or
                                     config=None, negative_prompt=None, guidance_rescale=0.0, sampler=None):
     """pipeline.py:213-267: same signature and defaults, plus `negative_prompt` (a string or one per prompt: its conditioning
     replaces the unconditional half of the guidance), `guidance_rescale` (phi of Lin et al. 2023) and a trailing `sampler` (None:
-    the reference's DDIM at eta 1; "dpmpp_2m": DPM-Solver++(2M), deterministic, so ddim_eta=0.0 travels with it).  Pass the three
+    the reference's DDIM at eta 1; "dpmpp_2m": DPM-Solver++(2M), deterministic, so ddim_eta=0.0 travels with it; "dpmpp_2m_sde": its SDE form
+    at ddim_eta=1.0).  Pass the three
     by keyword: `sampler` stays the last parameter, the two others sit in front of it.  `original_audio_file_path` may also be a 1-D
     float waveform at 16 kHz.  STFT/mel (a17), VAE encode (a18), masked DDIM, decode and vocoder all run
     on the HIP path."""
@@ -1665,7 +1674,7 @@ def text_to_audio(latent_diffusion, text, transcription="", seed=42, ddim_steps=
     (np.float32 [batchsize, 1, samples]), plus `negative_prompt` (a string or one per prompt: its conditioning replaces the
     unconditional half of the guidance), `guidance_rescale` (phi of Lin et al. 2023, in [0, 1]; 0: off) and a trailing `sampler`
     (None: the reference's DDIM at eta 1; "dpmpp_2m": DPM-Solver++(2M) over `ddim_steps`, deterministic, so ddim_eta=0.0 travels
-    with it).  Pass the three by keyword: `sampler` stays the last parameter, the two others sit in front of it."""
+    with it; "dpmpp_2m_sde": DPM-Solver++(2M) SDE, the stochastic second-order solver, with ddim_eta=1.0).  Pass the three by keyword: `sampler` stays the last parameter, the two others sit in front of it."""
     sampler_kw = _sampler_kwargs(sampler, negative_prompt, guidance_rescale)
     seed_everything(int(seed))
     batch = make_batch_for_text_to_audio(text, transcription=transcription, batchsize=batchsize)

@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 /* ---- library / error ------------------------------------------------------------------ */
-int aldm_version(void);              /* ABI version (25),bumped on any struct / entry change */
+int aldm_version(void);              /* ABI version (26),bumped on any struct / entry change */
 const char* aldm_last_error(void);   /* message of the last failing call on this thread     */
 
 /* ---- activations usable as prologue (applied to the gathered input) or epilogue -------- */
@@ -553,6 +553,21 @@ int aldm_plms_step_indexed(float* x, const float* eps, float* hist, const float*
  * The counter is not range-checked, as in aldm_ddim_step_indexed: aldm_step_advance saturates it at the last row.           */
 int aldm_dpmpp_step_indexed(float* x, const float* eps, float* x0_buf, const float* coef_tab, const int* step_idx, int64_t n,
                             int coef_ld, void* stream);
+/* DPM-Solver++(2M) SDE (Lu et al. 2022, the SDE variant in its midpoint form, generalised by eta in [0, 1]; ABI v26),
+ * in place on x.  s = *step_idx, coef = coef_tab[s] (rows of coef_ld >= 9 floats): columns 0-7 are exactly what
+ * aldm_dpmpp_step_indexed reads — {sigma_t, alpha_t, c2, c3, w, guidance_scale, use_cfg, phi} — with
+ *   c2 = (sigma_prev/sigma_t) exp(-eta h),  c3 = -alpha_prev expm1(-(1 + eta) h),  and column 8:  c4 = sigma_prev sqrt(-expm1(-2 eta h)).
+ *   e, x0, D as in aldm_dpmpp_step_indexed;  x = (c2*x + c3*D) + c4*z;  x0_buf = x0
+ * z = row clamp(s, 0, noise_rows - 1) of noise_tab [noise_rows, n], the step's unit noise (already scaled by a temperature): whatever
+ * the counter holds, the launch stays inside the table.  The coefficient row itself is not range-checked, as in
+ * aldm_dpmpp_step_indexed.  fp32, the formula's operation order, c4*z and the last sum rounded separately (no contraction): bitwise
+ * reproducible.  When c4 == 0 the noise element is not loaded — a NaN table cannot reach x — and the launch is bitwise
+ * aldm_dpmpp_step_indexed on the same first eight columns; when w == 0 the history slab is not loaded.  16-byte accesses when
+ * n % 4 == 0 and x, eps, x0_buf and noise_tab are 16-byte aligned (every row is then), else a scalar form; grid-stride, 64-bit
+ * indexing.  Refused before any launch: null pointers, n <= 0, noise_rows < 1, coef_ld < 9, x or x0_buf overlapping the noise table.
+ * No atomics, nothing kept between launches.                                                                                      */
+int aldm_dpmpp_sde_step_indexed(float* x, const float* eps, float* x0_buf, const float* noise_tab, int noise_rows,
+                                const float* coef_tab, const int* step_idx, int64_t n, int coef_ld, void* stream);
 /* Classifier-free guidance combine with guidance rescale (Lin et al. 2023, "Common Diffusion Noise Schedules and Sample Steps are
  * Flawed", section 3.4; ABI v14).  s = step_idx ? *step_idx : 0, coef = coef_tab[s] (rows of coef_ld >= 8 floats): coef[5] the
  * guidance scale g, coef[7] = phi.  eps holds [e_uncond ; e_cond] as [2, B, n_s]; per sample b over its n_s elements:
