@@ -80,6 +80,31 @@ the measured figures and are lowered in that file; the older tests of the same o
   ... mean / std = 100 | torch fp32 F.layer_norm on the CPU        2.0e-6 | 3.2e-6                        max(6e-7, 3 x torch's) = 9.5e-6
   RMSNorm, same shapes                                             8.3e-8 .. 1.6e-7                       8e-7
   row softmax, N = 1 .. 15360: plain | masked | biased             1.5e-7 .. 2.2e-7 | 7e-8 .. 2.0e-7 | 1.3e-7 .. 2.2e-7   9e-7
+
+The launch forms the VAE issues (audioldm2_amd/vae.py), one by one, against fp64 (tests/test_vae_forms_gpu.py,
+profiles/r14_vae_forms_errors.txt; two samples of 13 x 16 / 65 x 16 / 5 x 64 / 5 x 32 pixels, 128 .. 512 channels; the 3x3 convs on split
+operands on the planner's tile, a forced 128x128 tile and a forced halo form; the bars are the existing ones, set before these launches were
+measured on their own; typical .. worst):
+
+  quantity                                                        f32 (register-staged)  bf16x6               f16x3                bar    bf16x3              bar
+  ResnetBlock gn_split images, 3-part | fp16: excess over model    —                     1.2e-7 .. 1.9e-7     8e-9 .. 1.4e-8       9e-7 | 5e-7   4.5e-6 .. 7.2e-6   8.5e-6
+  1x1 nin_shortcut on the raw image                                2.8e-7 .. 5.0e-7       5.6e-7 .. 9.2e-7     (the same launch)    2e-6   5.0e-6 .. 5.6e-6    5e-5
+  conv1 / conv2 + skip vs fp64 of the image: planner               —                     2.8e-7 .. 9.2e-7     2.2e-7 .. 9.4e-7     2e-6   3.4e-6 .. 4.8e-6    5e-5
+  ... forced 128x128 tile, no split-K | forced halo form           —                     8.1e-7 .. 1.6e-6 | 8.6e-7 .. 1.2e-6   5.4e-7 .. 1.3e-6 | 5.7e-7 .. 7.8e-7   2e-6   3.5e-6 .. 4.7e-6   5e-5
+  ... vs fp64 GroupNorm + SiLU + conv (every form)                 2.4e-7 .. 6.8e-7       2.8e-7 .. 1.6e-6     2.2e-7 .. 1.3e-6     5e-6   4.3e-6 .. 5.7e-6    5e-5
+  ResnetBlock.run as a whole                                       3.5e-7 .. 6.9e-7       4.5e-7 .. 8.5e-7     4.3e-7 .. 7.9e-7     5e-6   6.4e-6 .. 7.5e-6    5e-5
+  fp16 image at n = 2^20 (C = 128, P = 262144; scale 2^3)          —                     —                    2.0e-7 of max|ref|, 4.5e-9 over the model; 1x1 conv from it 2.9e-7   5e-7; 5e-6
+  AttnBlock: qkv projection behind gn_split | the prologue         2.4e-7 .. 2.7e-7       5.8e-7 .. 8.0e-7 | 3.4e-7 .. 4.5e-7   6.4e-7 .. 7.2e-7   5e-6   4.7e-6 .. 4.9e-6    5e-5
+  ... gemm_nt on slices at pitch 3C | pack_kn + P V                2.3e-7 | 2.5e-7 .. 3.5e-7   2.0e-7 .. 2.6e-7 | 2.8e-7 .. 4.0e-7   (fp32 operands: as bf16x6)   2e-6   (as bf16x6)   5e-5
+  ... softmax_rows | out projection + residual | whole block       9e-8 | 9.5e-8 .. 9.9e-8 | 1.2e-7   1.0e-7 .. 1.3e-7 | 1.3e-7 .. 1.9e-7 | 1.7e-7 .. 2.3e-7   (as bf16x6)   9e-7 | 2e-6 | 5e-6   whole 2.2e-6 .. 2.8e-6   5e-5
+  gemm_nt / gemm_packed_batched at K = 3104, 3100                  2.5e-7 / 3.3e-7 .. 4.1e-7 in every mode; torch fp32 bmm 5.9e-7 .. 6.3e-7 / 9.7e-7 .. 1.3e-6             5e-6
+  Downsample (0, 1, 0, 1) + k3 s2: staged | planner | forced tile  2.1e-7 .. 2.4e-7       1.9e-7 .. 2.5e-7 | 2.5e-7 .. 2.8e-7 | 9.0e-7 .. 9.9e-7   (as bf16x6)   2e-6   4.5e-6 .. 4.8e-6    5e-5
+  Upsample nearest x2 + k3 p1: staged | planner | forced tile      3.0e-7 .. 3.5e-7       3.4e-7 .. 3.8e-7 | 4.6e-7 .. 5.4e-7 | 6.8e-7 .. 7.3e-7   (as bf16x6)   2e-6   4.3e-6 .. 4.5e-6    5e-5
+  Decoder.conv_out N = 1 (rows 4 bytes apart) | Encoder.conv_out   1.2e-6 .. 1.3e-6 | 2.7e-6 (N = 16), 3.1e-6 (N = 32): one register-staged kernel in every mode            5e-6
+  Decoder.conv_in K = 72 / 144 | Encoder.conv_in K = 36            3.2e-7 / 2.7e-7 | 1.5e-7   3.1e-7 / 2.8e-7 | 1.8e-7   (as bf16x6)                                       2e-6
+  VAE of ch = 128, (2, 8, 5, 16) latent: decode / encode pre-split 2.5e-6 / 1.6e-6        2.3e-6 / 1.7e-6      2.4e-6 / 1.5e-6      4e-5   3.6e-5 / 1.6e-5     2e-4
+  ... register-staged | torch fp32 on the CPU                      (the same)             2.6e-6 / 2.0e-6 | 1.9e-6 / 9.9e-7                4e-5
+  the five-product hook on the chain: skip | conv1 vs its image    1.1e-5 | 7.6e-6 (fail 2e-6; six products: 4.8e-7 | 1.0e-6)
 """
 import os
 
