@@ -53,7 +53,9 @@ def test_attn_block_restatement_equals_the_oracle():
     assert got["qkv"].shape == (vf.B, L, 3 * C) and got["scores"].shape == (vf.B, L, L) and got["o"].shape == (vf.B, L, C)
     assert float((got["probs"].sum(-1) - 1).abs().max()) < 1e-14
     q, k = got["qkv"][:, :, :C], got["qkv"][:, :, C:2 * C]
-    assert vf.max_rel(vf.attn_scores(q, k, C), got["scores"]) == 0.0
+    # (in the memory layout the restatement's own q and k have — [B, C, L] transposed — so that the CPU's BLAS sums the same way)
+    as_rows = lambda t: t.transpose(1, 2).contiguous().transpose(1, 2)
+    assert vf.max_rel(vf.attn_scores(as_rows(q), as_rows(k), C), got["scores"]) == 0.0
 
 
 def test_whole_decoder_and_encoder_out_of_the_restatements_equal_the_oracle(tiny):
