@@ -444,6 +444,58 @@ __global__ __launch_bounds__(kRescaleThreads) void cfg_rescale_indexed_kernel(co
     }
 }
 
+// ---- composable guidance (Liu et al. 2022, "Compositional Visual Generation with Composable Diffusion Models") --------------------
+// eps [(K+1), n]: group 0 the unconditional prediction, groups 1..K the prompts'.  Row r = clamp(*step_idx, 0, rows - 1) (row 0
+// without a counter) of w_tab [rows, K+1] = {c_0 = 1 - sum w_k, c_1 = w_1, ..., c_K = w_K}, so that
+//   e_c = sum_g c_g eps[g]  ==  e_u + sum_k w_k (eps[k] - e_u)
+// is the conditional half of the standard pair: the guidance scale multiplies the whole sum where the pair is combined, downstream.
+// The row is read once per thread, outside the element loop.  A group whose coefficient is exactly 0 is skipped BEFORE its element is
+// loaded (window_merge_rows_kernel's rule: no 0 * NaN, no traffic); the first kept term is a plain multiply, every later one one fma,
+// in ascending g; no kept term: 0.  K = 1, w = 1 is {0, 1}: e_c is eps[1] bit for bit.
+// pair: out[0:n] = eps[0] bitwise (not rewritten when out == eps) and out[n:2n] = e_c; else out[0:n] = e_c.  out may BE eps: a thread
+// owns element i of every group and stores only after it has loaded all of them.  eps and out are therefore not __restrict__.
+template <int W>
+__global__ void cfg_compose_indexed_kernel(const float* eps, float* out, const float* __restrict__ w_tab,
+                                           const int* __restrict__ step_idx, int rows, int K, int pair, int64_t n) {
+    int r = step_idx ? *step_idx : 0;
+    r = r < 0 ? 0 : (r > rows - 1 ? rows - 1 : r);
+    float c[ALDM_MAX_COMPOSE + 1];
+#pragma unroll
+    for (int g = 0; g <= ALDM_MAX_COMPOSE; ++g) c[g] = g <= K ? w_tab[(int64_t)r * (K + 1) + g] : 0.f;
+    const bool copy_u = pair && out != eps;
+    float* oc = out + (pair ? n : 0);
+    const int64_t nv = n / W;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nv; i += (int64_t)gridDim.x * blockDim.x) {
+        float acc[W], v[W];
+        bool any = false;
+#pragma unroll
+        for (int k = 0; k < W; ++k) acc[k] = 0.f;
+#pragma unroll
+        for (int g = 0; g <= ALDM_MAX_COMPOSE; ++g) {
+            if (c[g] == 0.f) continue;   // uniform over the grid: groups past K have c == 0 too
+            rescale_load<W>(eps + (int64_t)g * n + i * W, v);
+#pragma unroll
+            for (int k = 0; k < W; ++k) acc[k] = any ? __builtin_fmaf(c[g], v[k], acc[k]) : c[g] * v[k];
+            any = true;
+        }
+        if (copy_u) {
+            rescale_load<W>(eps + i * W, v);
+            if constexpr (W == 4) {
+                const f32x4 q = {v[0], v[1], v[2], v[3]};
+                *reinterpret_cast<f32x4*>(out + i * 4) = q;
+            } else {
+                out[i] = v[0];
+            }
+        }
+        if constexpr (W == 4) {
+            const f32x4 q = {acc[0], acc[1], acc[2], acc[3]};
+            *reinterpret_cast<f32x4*>(oc + i * 4) = q;
+        } else {
+            oc[i] = acc[0];
+        }
+    }
+}
+
 // last node of the step graph: counter += 1 and the NEXT step's timestep row into the UNet's static input (one block: every
 // thread reads the old counter before thread 0 stores the new one)
 __global__ void step_advance_kernel(int* __restrict__ step_idx, const float* __restrict__ t_tab, float* __restrict__ t_cur,
@@ -652,6 +704,31 @@ extern "C" int aldm_cfg_rescale_indexed(const float* eps, float* out, const floa
         hipLaunchKernelGGL(cfg_rescale_indexed_kernel<1>, dim3((unsigned)B), dim3(kRescaleThreads), 0, (hipStream_t)stream, eps, out,
                            coef_tab, step_idx, B, n_s, coef_ld);
     ALDM_LAUNCH_CHECK("aldm_cfg_rescale_indexed");
+    return 0;
+}
+
+extern "C" int aldm_cfg_compose_indexed(const float* eps, float* out, const float* w_tab, const int* step_idx, int rows, int K,
+                                        int pair, int64_t n, void* stream) {
+    ALDM_CHECK(eps && out && w_tab, "aldm_cfg_compose_indexed: null pointer");
+    ALDM_CHECK(K >= 1 && K <= ALDM_MAX_COMPOSE, "aldm_cfg_compose_indexed: K=%d prompts (1 <= K <= %d)", K, ALDM_MAX_COMPOSE);
+    ALDM_CHECK(rows >= 1, "aldm_cfg_compose_indexed: rows=%d: the weight table needs at least one row", rows);
+    ALDM_CHECK(pair == 0 || pair == 1, "aldm_cfg_compose_indexed: pair=%d must be 0 or 1", pair);
+    ALDM_CHECK(n > 0 && n <= (1ll << 40), "aldm_cfg_compose_indexed: bad args (n=%lld)", (long long)n);
+    const uintptr_t nb = (uintptr_t)n * sizeof(float);
+    const uintptr_t e0 = (uintptr_t)eps, e1 = e0 + (uintptr_t)(K + 1) * nb;
+    const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (uintptr_t)(pair ? 2 : 1) * nb;
+    const uintptr_t t0 = (uintptr_t)w_tab, t1 = t0 + (uintptr_t)rows * (uintptr_t)(K + 1) * sizeof(float);
+    // in place is the one legal overlap: a thread stores element i only after it has loaded element i of every group
+    ALDM_CHECK(o0 == e0 || o1 <= e0 || e1 <= o0, "aldm_cfg_compose_indexed: out overlaps eps (only out == eps, in place, is allowed)");
+    ALDM_CHECK(o1 <= t0 || t1 <= o0, "aldm_cfg_compose_indexed: out overlaps w_tab");
+    const bool vec = n % 4 == 0 && ((e0 | o0) & 15) == 0;
+    if (vec)
+        hipLaunchKernelGGL(cfg_compose_indexed_kernel<4>, dim3(ew_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, eps, out, w_tab,
+                           step_idx, rows, K, pair, n);
+    else
+        hipLaunchKernelGGL(cfg_compose_indexed_kernel<1>, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, eps, out, w_tab,
+                           step_idx, rows, K, pair, n);
+    ALDM_LAUNCH_CHECK("aldm_cfg_compose_indexed");
     return 0;
 }
 

@@ -210,6 +210,11 @@ class DDIMSampler(SamplerBase):
                 # the starts are kernel arguments of the captured gather and merge nodes
                 from .windows import plan_key
                 key = key + (plan_key(windows),)
+            if plan.compose is not None:
+                # composable guidance: K and the table's row count are kernel arguments of the captured compose node; the weight
+                # VALUES live in the entry's table, refilled per job.  A K = 1 job has a plain guided job's context shapes, not its
+                # launch sequence: the marker keeps the two apart
+                key = key + (("compose",) + tuple(plan.compose.shape),)
         ent = unet._graph_cache.get(key) if can_cache else None
         if ent is not None and ent.get("kv") is None:
             # the entry never got as far as recording the K/V buffers its graph reads (e.g. an interrupted first run)
@@ -233,6 +238,9 @@ class DDIMSampler(SamplerBase):
                 # a phased ring plan: the captured gather and merge nodes read the entry's phase table; this job's phases go INTO
                 # it (the key holds "phased" and the step count, not the values), outside any capture
                 ent["win"].phase.copy_(plan.win.phase)
+            if plan.compose is not None:
+                # composable guidance: the captured compose node reads the entry's table; this job's weights go INTO it
+                ent["compose"].copy_(plan.compose)
         else:
             # static buffers = the graph's inputs
             ent = {"x_cur": img.clone(), "pred_x0": torch.empty_like(img), "t_cur": plan.t_tab[0].clone(),
@@ -250,6 +258,9 @@ class DDIMSampler(SamplerBase):
             if plan.win is not None and plan.win.phase is not None:
                 # moving window phases: the gather and merge nodes select the visit's phase with the graph's step counter
                 plan.win.step_idx = ent["step_idx"]
+            if plan.compose is not None:
+                # composable guidance: the compose node behind the UNet pass selects the visit's weights with the graph's counter
+                ent["compose"], cond.step_idx = plan.compose, ent["step_idx"]
 
             def step(e=ent):
                 x_c = e["x_cur"]

@@ -207,6 +207,9 @@ class DPMSolverSampler(SamplerBase):
         if plan.win is not None and plan.win.phase is not None:
             # moving window phases: the gather and merge nodes select the step's phase with the counter
             plan.win.step_idx = step_idx
+        if plan.compose is not None:
+            # composable guidance: the compose node behind the UNet pass selects the step's weights with the counter
+            cond.step_idx = step_idx
 
         def step():
             eps = self.model_output(x_cur, t_cur, b, cond, unconditional_conditioning, use_cfg, prepared, win=plan.win)

@@ -1643,6 +1643,41 @@ def cfg_rescale_indexed(eps: torch.Tensor, out: torch.Tensor, coef: torch.Tensor
     return out
 
 
+MAX_COMPOSE = 8   # ALDM_MAX_COMPOSE of include/aldm_hip.h
+
+
+def cfg_compose_indexed(eps: torch.Tensor, w_tab: torch.Tensor, step_idx: Optional[torch.Tensor] = None, pair: bool = True,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Composable guidance (aldm_cfg_compose_indexed; Liu et al. 2022): the K+1 predictions eps [(K+1), ...] of one
+    UNet pass — group 0 unconditional, groups 1..K the prompts' — reduced to the standard pair.  w_tab [rows, K+1] holds
+    {c_0 = 1 - sum w_k, w_1, ..., w_K} per row (sampling.compose_table); the int32 device counter `step_idx` selects the row, clamped
+    into the table (None: row 0).  e_c = sum_g c_g eps[g], zero coefficients skipped before the load.  pair=True -> [2, ...] =
+    [eps[0] ; e_c]; pair=False -> [...] = e_c.  out=None: in place, the result is a view of eps' first groups; an `out` of that shape
+    may share no byte with eps.  -> the result."""
+    for t, n in ((eps, "eps"), (w_tab, "w_tab")) + (() if out is None else ((out, "out"),)):
+        _chk(t, "cfg_compose." + n)
+    if eps.dim() < 2 or not 2 <= eps.shape[0] <= MAX_COMPOSE + 1 or eps.numel() == 0:
+        raise RuntimeError(f"cfg_compose: eps must be [(K+1), ...] with 1 <= K <= {MAX_COMPOSE}, got {tuple(eps.shape)}")
+    G = eps.shape[0]
+    if w_tab.dim() != 2 or w_tab.shape[1] != G or w_tab.shape[0] < 1:
+        raise RuntimeError(f"cfg_compose.w_tab: expected a [rows, {G}] table, got {tuple(w_tab.shape)}")
+    if step_idx is not None and not (step_idx.dtype == torch.int32 and step_idx.is_cuda and step_idx.numel() == 1):
+        raise RuntimeError(f"cfg_compose.step_idx: expected one int32 CUDA element, got {step_idx.dtype} {step_idx.device} "
+                           f"numel={step_idx.numel()}")
+    shape = ((2,) if pair else ()) + tuple(eps.shape[1:])
+    if out is None:
+        res = eps[:2] if pair else eps[0]
+        dst = eps
+    else:
+        if tuple(out.shape) != shape:
+            raise RuntimeError(f"cfg_compose.out: expected {shape}, got {tuple(out.shape)}")
+        _no_overlap(out, "cfg_compose.out", [(eps, "eps")])
+        res = dst = out
+    _l.check(_l.load().aldm_cfg_compose_indexed(eps.data_ptr(), dst.data_ptr(), w_tab.data_ptr(), _p(step_idx), w_tab.shape[0],
+                                                G - 1, 1 if pair else 0, eps.numel() // G, _stream()), "cfg_compose_indexed")
+    return res
+
+
 def step_advance(step_idx: torch.Tensor, t_tab: torch.Tensor, t_cur: torch.Tensor) -> None:
     """step_idx += 1; t_cur = t_tab[min(step_idx, S - 1)] on the device (aldm_step_advance)."""
     _chk(t_tab, "step_advance.t_tab"); _chk(t_cur, "step_advance.t_cur")

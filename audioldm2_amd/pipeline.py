@@ -341,6 +341,117 @@ def timeline_frames(timeline, per_second, latent_t):
     return prompts, transcriptions, boundaries
 
 
+def _schedule_weights(w, ddim_steps, ld, who):
+    """A composed job's weights against the `ddim_steps` schedule: [K] passes through; [ddim_steps, K] becomes one row per entry of
+    the schedule — the reference's uniform grid has one entry more than ddim_steps where ddim_steps does not divide the model's
+    timesteps, and the last row is repeated for it (phased_plan's rule).  ValueError for any other length."""
+    if w.ndim == 1:
+        return w
+    from .sampling import make_ddim_timesteps
+    n = len(make_ddim_timesteps("uniform", int(ddim_steps), int(ld.num_timesteps), verbose=False))
+    if w.shape[0] not in (int(ddim_steps), n):
+        raise ValueError(f"{who}: a weight list has {w.shape[0]} entries for ddim_steps={ddim_steps}: one per sampler step")
+    if w.shape[0] < n:
+        w = np.concatenate([w, np.repeat(w[-1:], n - w.shape[0], axis=0)], axis=0)
+    return w
+
+
+def compose_entries(compose, ddim_steps, ld, who="compose"):
+    """Pure host: the `compose=` keyword of the entry points (composable guidance) — [(prompt, weight) | (prompt,
+    weight, transcription), ...], a weight a finite number or a list of `ddim_steps` numbers in sampler order (the noisiest step
+    first) — -> (prompts, transcriptions, weights: fp64 [K], or [schedule length, K] when any weight is a list).  ValueError: an
+    empty list, more than sampling.MAX_COMPOSE entries, a malformed entry, a weight that is not finite, a list of the wrong length,
+    every weight 0 at some step, a list without ddim_steps."""
+    from .sampling import MAX_COMPOSE, check_compose_weights
+    entries = list(compose) if isinstance(compose, (list, tuple)) else None
+    if not entries:
+        raise ValueError(f"{who}: compose= needs a non-empty list of (prompt, weight) entries")
+    if len(entries) > MAX_COMPOSE:
+        raise ValueError(f"{who}: compose= takes at most {MAX_COMPOSE} entries, got {len(entries)}")
+    prompts, transcriptions, cols, listed = [], [], [], False
+    for e in entries:
+        if not isinstance(e, (list, tuple)) or len(e) not in (2, 3) or not isinstance(e[0], str) \
+                or (len(e) == 3 and not isinstance(e[2], str)):
+            raise ValueError(f"{who}: a compose= entry is (prompt, weight) or (prompt, weight, transcription), got {e!r}")
+        wk = e[1]
+        if isinstance(wk, (list, tuple, np.ndarray)):
+            if ddim_steps is None:
+                raise ValueError(f"{who}: a weight list needs ddim_steps: one weight per sampler step")
+            if len(wk) != int(ddim_steps):
+                raise ValueError(f"{who}: a weight list has {len(wk)} entries for ddim_steps={ddim_steps}: one per sampler step")
+            listed = True
+        elif isinstance(wk, (bool, str)) or not isinstance(wk, (int, float, np.integer, np.floating)):
+            raise ValueError(f"{who}: a weight must be a finite number or a list of ddim_steps numbers, got {wk!r}")
+        prompts.append(e[0])
+        transcriptions.append(e[2] if len(e) == 3 else "")
+        cols.append(wk)
+    try:
+        if listed:
+            cols = [np.asarray(c, dtype=np.float64) if isinstance(c, (list, tuple, np.ndarray))
+                    else np.full(int(ddim_steps), float(c)) for c in cols]
+            w = np.stack(cols, axis=1)
+        else:
+            w = np.asarray([float(c) for c in cols], dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: a weight must be a finite number or a list of ddim_steps numbers")
+    w = check_compose_weights(w, len(prompts), who)
+    return prompts, transcriptions, _schedule_weights(w, ddim_steps, ld, who)
+
+
+def _compose_batches(batch, weights, ddim_steps, unconditional_guidance_scale, unconditional_conditioning, n_gen, shard, boundaries,
+                     ld, who):
+    """The `batch` / `weights=` arguments of a generate_batch* job -> (the K batches of a composed job, or None; the batch whose mel,
+    file names and negative prompt the job takes: the first; the weights, fp64).  Without `weights`: (None, batch, None), today's
+    call.  Pure host; ValueError for a composed job that cannot run — see compose_entries and the entry points' docstrings."""
+    if weights is None:
+        return None, batch, None
+    from .sampling import MAX_COMPOSE, check_compose_weights
+    if boundaries is not None and len(list(boundaries)) > 0:
+        raise ValueError(f"{who}: weights= (composed prompts) together with boundaries= (a prompt timeline) is not supported")
+    if not isinstance(batch, (list, tuple)) or not batch:
+        raise ValueError(f"{who}: weights= needs `batch` to be a non-empty list of batches, one per composed prompt")
+    batches = list(batch)
+    if len(batches) > MAX_COMPOSE:
+        raise ValueError(f"{who}: at most {MAX_COMPOSE} composed prompts, got {len(batches)}")
+    sizes = [len(b["text"]) for b in batches]
+    if len(set(sizes)) != 1:
+        raise ValueError(f"{who}: the batches of a composed job must have one size, got {sizes}")
+    if ddim_steps is None:
+        raise ValueError(f"{who}: composed prompts need ddim_steps: the ancestral sampler has no guidance")
+    if n_gen != 1:
+        raise ValueError(f"{who}: composed prompts with n_gen={n_gen}: CLAP re-ranking of a composed job is not supported "
+                         "(n_candidate_gen_per_text must be 1)")
+    if shard is not None:
+        raise ValueError(f"{who}: composed prompts together with shard= are not supported")
+    if unconditional_guidance_scale == 1.0 and unconditional_conditioning is None:
+        raise ValueError(f"{who}: composed prompts need an unconditional conditioning (1 - sum(weights) weighs it): use a guidance "
+                         "scale != 1.0, or pass unconditional_conditioning=")
+    w = check_compose_weights(weights, len(batches), who)
+    return batches, batches[0], _schedule_weights(w, ddim_steps, ld, who)
+
+
+def _compose_entry(latent_diffusion, text, transcription, compose, ddim_steps, guidance_scale, n_gen, timeline, who, make_one):
+    """The `text` / `compose=` arguments of the entry points -> (the keywords a composed job adds to generate_batch*, a callable
+    making the list of batches after the seed is set — or None without `compose`).  make_one(prompt, transcription) makes one batch.
+    Everything a composed job can be refused for is refused here, on the host, before the seed is set."""
+    if compose is None:
+        return {}, None
+    if text is not None or transcription:
+        raise ValueError(f"{who}: with compose= the prompts (and transcriptions) are the list's: pass text=None")
+    if timeline is not None:
+        raise ValueError(f"{who}: compose= together with timeline= is not supported")
+    if n_gen != 1:
+        raise ValueError(f"{who}: compose= with n_candidate_gen_per_text={n_gen}: CLAP re-ranking of a composed job is not "
+                         "supported, pass n_candidate_gen_per_text=1")
+    if ddim_steps is None:
+        raise ValueError(f"{who}: compose= needs ddim_steps: the ancestral sampler has no guidance")
+    if guidance_scale == 1.0:
+        raise ValueError(f"{who}: compose= needs an unconditional conditioning (1 - sum(weights) weighs it): guidance_scale must "
+                         "not be 1.0")
+    prompts, transcriptions, w = compose_entries(compose, ddim_steps, latent_diffusion, who)
+    return {"weights": w}, lambda: [make_one(p, t) for p, t in zip(prompts, transcriptions)]
+
+
 def resolve_sampler(sampler, use_plms=False):
     """The `sampler=` keyword of sample_log / generate_batch / generate_batch_masked / text_to_audio /
     super_resolution_and_inpainting: None (the reference's behaviour) or a name in SAMPLERS, not together with use_plms=True."""
@@ -708,6 +819,45 @@ class LatentDiffusion(nn.Module):
                                          context_attn_mask_list=prepared["masks"])
         return eps.view(2, B, *eps.shape[1:])
 
+    @torch.no_grad()
+    def prepare_groups(self, conds, uncond):
+        """prepare_cfg over G = K+1 conditioning groups [uncond ; conds[0] ; ... ; conds[K-1]] (composable guidance):
+        the same zero-padding to a common context length with mask 0 on the padding, the same persistent tensors — contexts, masks
+        and y of G*B rows, group-major — for the UNet to keep its cross-attention K/V projections over the run."""
+        routed = [DiffusionWrapper.route(self.reorder_cond_dict(c)) for c in [uncond] + list(conds)]
+        ctxs, masks = [], []
+        for j in range(len(routed[0][1])):
+            L = max(r[1][j].shape[1] for r in routed)
+            cs, ms = [], []
+            for r in routed:
+                c = r[1][j].float()
+                m = r[2][j].float().reshape(c.shape[0], -1)
+                if c.shape[1] < L:
+                    c = torch.cat([c, c.new_zeros(c.shape[0], L - c.shape[1], c.shape[2])], 1)
+                    m = torch.cat([m, m.new_zeros(m.shape[0], L - m.shape[1])], 1)
+                cs.append(c)
+                ms.append(m)
+            ctxs.append(torch.cat(cs, 0).contiguous())
+            masks.append(torch.cat(ms, 0).contiguous())
+        y = None if routed[0][0] is None else torch.cat([r[0] for r in routed], 0).float().contiguous()
+        return {"ctxs": ctxs, "masks": masks, "y": y, "groups": len(routed)}
+
+    @torch.no_grad()
+    def apply_model_groups(self, x, t_row, prepared):
+        """One UNet pass over the G groups of `prepared` = prepare_groups(conds, uncond) on the same x [B, ...] and the same t: eps
+        [G, B, C, H, W], group 0 the unconditional prediction.  t_row: the step's timestep as floats, B entries or G*B.  Like
+        apply_model_cfg the UNet runs its context-free prefix once for all groups; ALDM_CFG_SHARE=0 keeps the pass over x repeated
+        G times."""
+        G, B = prepared["groups"], x.shape[0]
+        t = t_row if t_row.shape[0] == G * B else t_row[:B].repeat(G)
+        if os.environ.get("ALDM_CFG_SHARE", "1") != "0":
+            eps = self.model.diffusion_model(x.contiguous(), t, context_list=prepared["ctxs"], y=prepared["y"],
+                                             context_attn_mask_list=prepared["masks"], cfg_shared=True)
+        else:
+            eps = self.model.diffusion_model(x.repeat(G, 1, 1, 1).contiguous(), t, context_list=prepared["ctxs"], y=prepared["y"],
+                                             context_attn_mask_list=prepared["masks"])
+        return eps.view(G, B, *eps.shape[1:])
+
     def _apply_model_cfg_two_streams(self, x, t2, prepared):
         """Opt-in (ALDM_CFG_STREAMS=1): the uncond and cond halves as two concurrent branches (two HIP
         streams = parallel branches of the captured graph), each with its own context length.  Measured on
@@ -747,6 +897,9 @@ class LatentDiffusion(nn.Module):
             kwargs.pop("guidance_rescale", None)   # off: today's call, unchanged
         elif not (use_plms or sampler_name is not None or ddim):
             raise ValueError("guidance_rescale needs ddim_steps: the ancestral sampler has no guidance")
+        from .sampling import Composed
+        if isinstance(cond, Composed) and not (use_plms or sampler_name is not None or ddim):
+            raise ValueError("a Composed conditioning needs ddim_steps: the ancestral sampler has no guidance")
         # `t_start` (a keyword of **kwargs: run only the schedule's first t_start entries from x_T) goes to whichever of the three
         # samplers runs; the start latent then sets the shape
         t_start = kwargs.get("t_start", None)
@@ -1019,9 +1172,21 @@ class LatentDiffusion(nn.Module):
                        **kwargs):
         """ddpm.py:1477-1570 (text-to-audio).  RNG contract R: the reference encodes an all-zero mel and
         draws the posterior sample (one CPU randn of the latent shape, distributions.py:37-41) only to
-        read its batch size; we replay the draw and skip the 345 GFLOP encode."""
+        read its batch size; we replay the draw and skip the 345 GFLOP encode.
+
+        Composed prompts (composable guidance, Liu et al. 2022): `batch` a LIST of K <= 8 batches of equal size, one per
+        prompt, with `weights=` (a keyword of **kwargs like `sampler`): [K] finite numbers, or [ddim_steps, K] — one row per sampler
+        step, the noisiest first.  The model's prediction becomes e_u + scale * sum_k w_k (e_k - e_u) on one UNet pass over K+1
+        conditioning groups (sampling.Composed); generate_batch_masked and generate_batch_from_audio take the same pair, the first
+        batch carrying the mel.  The conditioners run once per prompt in list order, then the negative prompt's; no other draw moves.
+        Refused before any draw: n_gen != 1, shard=, ddim_steps=None, scale 1.0 without unconditional_conditioning, batches of unequal
+        size, weights that are not finite, of the wrong shape, or all 0 at some step."""
         assert x_T is None
         sampler = resolve_sampler(kwargs.get("sampler", None), use_plms)   # travels in **kwargs like `shard`
+        # composed prompts (DESIGN.md 9m; `weights` travels in **kwargs too): `batch` a list of K batches, one per prompt
+        batches, batch, weights = _compose_batches(batch, kwargs.get("weights", None), ddim_steps, unconditional_guidance_scale,
+                                                   unconditional_conditioning, n_gen, kwargs.get("shard", None), None, self,
+                                                   "generate_batch")
         neg_batch, guidance_rescale = _guidance_kwargs(kwargs, unconditional_guidance_scale, batch, ddim_steps)
         if use_plms:
             assert ddim_steps is not None
@@ -1034,9 +1199,10 @@ class LatentDiffusion(nn.Module):
         f = 2 ** (self.first_stage_model.encoder.num_resolutions - 1)
         torch.randn((B0, self.first_stage_model.embed_dim, fb.shape[-2] // f, fb.shape[-1] // f))  # (R1) draw & discard
         self._cfg_dropout_draw()                                                                     # (R1b) every call but the first
-        c = self.get_learned_conditioning_dict(batch)
         batch_size = B0 * n_gen
-        c = _tile_cond(c, n_gen)
+        # a composed job: the conditioners once per prompt, in list order, then the negative prompt's (n_gen == 1: nothing to tile)
+        c = self._compose_cond(batches, weights) if batches is not None else _tile_cond(self.get_learned_conditioning_dict(batch),
+                                                                                        n_gen)
         text = list(batch["text"]) * n_gen
         unconditional_conditioning = _unconditional_half(self, neg_batch, n_gen, batch_size, unconditional_guidance_scale,
                                                          unconditional_conditioning)
@@ -1096,6 +1262,10 @@ class LatentDiffusion(nn.Module):
                 raise ValueError("levels= needs ddim_steps: the ancestral sampler has no graded keep levels")
             check_levels(levels, levels, "generate_batch_masked(levels=)")
         sampler = resolve_sampler(kwargs.get("sampler", None), use_plms)
+        # composed prompts: `batch` a list of K batches with `weights=` in **kwargs; the first carries the mel
+        batches, batch, weights = _compose_batches(batch, kwargs.get("weights", None), ddim_steps, unconditional_guidance_scale,
+                                                   unconditional_conditioning, n_gen, kwargs.get("shard", None), None, self,
+                                                   "generate_batch_masked")
         neg_batch, guidance_rescale = _guidance_kwargs(kwargs, unconditional_guidance_scale, batch, ddim_steps)
         resample = check_resample_job(kwargs.get("resample", None), ddim_steps, sampler, use_plms, self)
         if use_plms:
@@ -1107,7 +1277,7 @@ class LatentDiffusion(nn.Module):
         x = fb.unsqueeze(1).float().contiguous().to(self.device)  # DDPM.get_input: [B, 1, T, F]
         z = self.get_first_stage_encoding(self.encode_first_stage(x))  # (R1) posterior draw, really used here
         self._cfg_dropout_draw()                                        # (R1b) every call but the first
-        c = self.get_learned_conditioning_dict(batch)
+        c = self._compose_cond(batches, weights) if batches is not None else self.get_learned_conditioning_dict(batch)
         B0 = z.shape[0]
         batch_size = B0 * n_gen
         h, w = z.shape[2], z.shape[3]
@@ -1122,7 +1292,8 @@ class LatentDiffusion(nn.Module):
             except RuntimeError:
                 raise ValueError(f"levels= must broadcast to [B, 1, h, w] = {(batch_size, 1, h, w)}, got {tuple(levels.shape)}")
             graded_kw["graded"] = True
-        c = _tile_cond(c, n_gen)
+        if batches is None:
+            c = _tile_cond(c, n_gen)
         text = list(batch["text"]) * n_gen
         unconditional_conditioning = _unconditional_half(self, neg_batch, n_gen, batch_size, unconditional_guidance_scale,
                                                          unconditional_conditioning)
@@ -1154,6 +1325,10 @@ class LatentDiffusion(nn.Module):
         if ddim_steps is None:
             raise ValueError("generate_batch_from_audio needs ddim_steps: the ancestral sampler has no shortened schedule")
         sampler = resolve_sampler(kwargs.get("sampler", None), use_plms)
+        # composed prompts: `batch` a list of K batches with `weights=` in **kwargs; the first carries the mel.  A
+        # weight list covers the whole ddim_steps schedule: the run reads the rows of the t_enc steps it makes
+        batches, batch, weights = _compose_batches(batch, kwargs.get("weights", None), ddim_steps, unconditional_guidance_scale,
+                                                   None, n_gen, None, None, self, "generate_batch_from_audio")
         neg_batch, guidance_rescale = _guidance_kwargs(kwargs, unconditional_guidance_scale, batch, ddim_steps)
         t_enc, _, sa, so = sdedit_plan(strength, ddim_steps, self.alphas_cumprod, self.num_timesteps)
         self._check_candidates(n_gen, batch.get("text"))
@@ -1164,9 +1339,9 @@ class LatentDiffusion(nn.Module):
         B0, h, w, C = moments.shape[0], moments.shape[1], moments.shape[2], moments.shape[3] // 2
         n_post = torch.randn((B0, C, h, w))                        # (R1) the posterior draw
         self._cfg_dropout_draw()                                   # (R1b) every call but the first
-        c = self.get_learned_conditioning_dict(batch)
         batch_size = B0 * n_gen
-        c = _tile_cond(c, n_gen)
+        c = self._compose_cond(batches, weights) if batches is not None else _tile_cond(self.get_learned_conditioning_dict(batch),
+                                                                                        n_gen)
         text = list(batch["text"]) * n_gen
         unconditional_conditioning = _unconditional_half(self, neg_batch, n_gen, batch_size, unconditional_guidance_scale)
         n_enc = torch.randn((batch_size, C, h, w))                 # the forward-diffusion noise, in the place of the x_T draw
@@ -1203,7 +1378,8 @@ class LatentDiffusion(nn.Module):
     @torch.no_grad()
     def generate_batch_long(self, batch, latent_t_size, hop=None, ddim_steps=200, ddim_eta=1.0, unconditional_guidance_scale=1.0,
                             unconditional_conditioning=None, use_plms=False, sampler=None, negative_prompt=None,
-                            guidance_rescale=0.0, n_gen=1, shard=None, loop=False, boundaries=None, transition=0.0, phase=None):
+                            guidance_rescale=0.0, n_gen=1, shard=None, loop=False, boundaries=None, transition=0.0, phase=None,
+                            weights=None):
         """Long-form text-to-audio by windowed diffusion (MultiDiffusion, Bar-Tal et al. 2023): ONE long latent of
         `latent_t_size` frames; at every step the UNet runs on overlapping windows of `self.latent_t_size` frames — the trained
         length, `hop` frames apart (default 3*Tw//4) — in one pass over W*b rows, the windows' outputs are fused by a tapered,
@@ -1222,6 +1398,10 @@ class LatentDiffusion(nn.Module):
         the rows are fused per frame by taper times prompt weight (ops.window_merge on the row plan).  The tail is unchanged:
         it runs on the plan without rows, the decode does not depend on prompts.  K = 1 is the run without a timeline, bit for
         bit.  The negative prompt and the (R1) shape are those of the first batch.  Not together with loop=True.
+
+        Composed prompts: `batch` a list of K batches with `weights=` ([K], or [ddim_steps, K]) instead of
+        `boundaries=` — all K prompts on every frame of every window, as in generate_batch; the compose launch runs on the window rows
+        in front of the merge, so it works on a linear plan, with loop=True and with phase=.  Not together with a timeline.
 
         `loop=True`: a clip that loops without a seam.  Sampling runs on the RING plan of the same numbers
         (long_form_plans(..., ring=True)): the window starts are spread round a circle of `latent_t_size` frames and windows wrap
@@ -1253,6 +1433,10 @@ class LatentDiffusion(nn.Module):
         draws exactly what the linear job draws, in the same order: a ring changes which frames a window sees, not a draw.  A
         timeline: the conditioners' draws come once per prompt, in timeline order, then the negative prompt's; everything else
         is unchanged."""
+        # composed prompts (DESIGN.md §9m): `batch` a list of K batches with `weights=` — all K prompts on every frame, where a
+        # timeline (boundaries=) gives each frame its own; on a linear plan or a ring (loop=True), with or without phase=
+        composed, batch, weights = _compose_batches(batch, weights, ddim_steps, unconditional_guidance_scale,
+                                                    unconditional_conditioning, n_gen, shard, boundaries, self, "generate_batch_long")
         batches, batch = _timeline_batches(batch, boundaries, loop, "generate_batch_long")
         if shard is not None:
             raise ValueError("generate_batch_long: shard= is not supported on this path")
@@ -1273,7 +1457,8 @@ class LatentDiffusion(nn.Module):
         f = 2 ** (self.first_stage_model.encoder.num_resolutions - 1)
         torch.randn((B0, self.first_stage_model.embed_dim, fb.shape[-2] // f, fb.shape[-1] // f))  # (R1) draw & discard
         self._cfg_dropout_draw()                                                                     # (R1b) every call but the first
-        c = self._timeline_cond(batches) if batches is not None else self.get_learned_conditioning_dict(batch)
+        c = self._compose_cond(composed, weights) if composed is not None else \
+            self._timeline_cond(batches) if batches is not None else self.get_learned_conditioning_dict(batch)
         unconditional_conditioning = _unconditional_half(self, neg_batch, 1, B0, unconditional_guidance_scale,
                                                          unconditional_conditioning)
         samples, _ = self.sample_log(cond=c, batch_size=B0, x_T=None, ddim=True, ddim_steps=ddim_steps, eta=ddim_eta,
@@ -1281,6 +1466,11 @@ class LatentDiffusion(nn.Module):
                                      unconditional_conditioning=unconditional_conditioning, use_plms=use_plms, windows=run_plan,
                                      **_sample_log_keywords(sampler, guidance_rescale))
         return self._long_tail(samples, plan, mel_plan, batch)
+
+    def _compose_cond(self, batches, weights):
+        """The conditioners on every prompt of a composed job, in list order (the order of their host-generator draws)."""
+        from .sampling import Composed
+        return Composed([self.get_learned_conditioning_dict(b) for b in batches], weights)
 
     def _timeline_cond(self, batches):
         """The conditioners on every prompt of a timeline, in timeline order (the order of their host-generator draws)."""
@@ -1339,7 +1529,7 @@ class LatentDiffusion(nn.Module):
     def generate_batch_long_from_audio(self, batch, latent_t_size, keep, hop=None, ddim_steps=200, ddim_eta=1.0,
                                        unconditional_guidance_scale=1.0, use_plms=False, sampler=None, negative_prompt=None,
                                        guidance_rescale=0.0, n_gen=1, shard=None, loop=False, boundaries=None, transition=0.0,
-                                       feather=0, phase=None, resample=None):
+                                       feather=0, phase=None, weights=None, resample=None):
         """Continuation and inpainting of long clips: generate_batch_long around a source.  `batch["log_mel_spec"]`
         is the long mel [B0, latent_t_size*f, F_mel] of the source; `keep` lists the half-open latent-frame intervals [a, b) to
         keep (windows.keep_mask); everything else is generated under the prompt.  The source is encoded window by window
@@ -1388,6 +1578,9 @@ class LatentDiffusion(nn.Module):
         the conditioners' draws once per prompt in timeline order, then the negative prompt's.  With `resample`, "per step" reads
         "per visit": the same two draws for each of the V visits, a renoise visit's q-noise drawn and not read."""
         from .windows import keep_levels, keep_mask, with_source
+        # composed prompts (DESIGN.md §9m), as in generate_batch_long: the FIRST batch carries the source's mel
+        composed, batch, weights = _compose_batches(batch, weights, ddim_steps, unconditional_guidance_scale, None, n_gen, shard,
+                                                    boundaries, self, "generate_batch_long_from_audio")
         batches, batch = _timeline_batches(batch, boundaries, loop, "generate_batch_long_from_audio")
         if shard is not None:
             raise ValueError("generate_batch_long_from_audio: shard= is not supported on this path")
@@ -1418,7 +1611,8 @@ class LatentDiffusion(nn.Module):
         B0 = fb.shape[0]
         n_post = torch.randn((B0, self.first_stage_model.embed_dim, plan.T, fb.shape[-1] // f))   # (R1) the posterior draw, long
         self._cfg_dropout_draw()                                                                    # (R1b) every call but the first
-        c = self._timeline_cond(batches) if batches is not None else self.get_learned_conditioning_dict(batch)
+        c = self._compose_cond(composed, weights) if composed is not None else \
+            self._timeline_cond(batches) if batches is not None else self.get_learned_conditioning_dict(batch)
         unconditional_conditioning = _unconditional_half(self, neg_batch, 1, B0, unconditional_guidance_scale)
         z = self.encode_long(fb.unsqueeze(1).float().contiguous().to(self.device), plan, mel_plan, n_post.to(self.device))
         self.last_long_source = z
@@ -1669,25 +1863,38 @@ def build_model(ckpt_path=None, config=None, device=None, model_name="audioldm2-
 
 def text_to_audio(latent_diffusion, text, transcription="", seed=42, ddim_steps=200, duration=10,
                   batchsize=1, guidance_scale=3.5, n_candidate_gen_per_text=3, latent_t_per_second=25.6,
-                  config=None, negative_prompt=None, guidance_rescale=0.0, sampler=None):
+                  compose=None, config=None, negative_prompt=None, guidance_rescale=0.0, sampler=None):
     """pipeline.py:181-211: same signature, side effects (sets latent_t_size) and return value
     (np.float32 [batchsize, 1, samples]), plus `negative_prompt` (a string or one per prompt: its conditioning replaces the
     unconditional half of the guidance), `guidance_rescale` (phi of Lin et al. 2023, in [0, 1]; 0: off) and a trailing `sampler`
     (None: the reference's DDIM at eta 1; "dpmpp_2m": DPM-Solver++(2M) over `ddim_steps`, deterministic, so ddim_eta=0.0 travels
-    with it; "dpmpp_2m_sde": DPM-Solver++(2M) SDE, the stochastic second-order solver, with ddim_eta=1.0).  Pass the three by keyword: `sampler` stays the last parameter, the two others sit in front of it."""
+    with it; "dpmpp_2m_sde": DPM-Solver++(2M) SDE, the stochastic second-order solver, with ddim_eta=1.0).  Pass the three by keyword: `sampler` stays the last parameter, the two others sit in front of it.
+
+    `compose` (composable guidance, Liu et al. 2022): several prompts on the SAME frames —
+    [("rain on a tin roof", 1.0), ("distant thunder", 0.6), ("traffic", -0.4)], entries (prompt, weight) or (prompt, weight,
+    transcription), passed by keyword (it sits in front of `config`, whose place among the last four parameters is pinned); `text`
+    must then be None (and `transcription` empty).  The model's prediction becomes
+    e_u + guidance_scale * sum_k w_k (e_k - e_u): a negative weight steers away from its prompt, `negative_prompt` still replaces
+    e_u, and a weight may be a list of `ddim_steps` numbers, one per sampler step (the noisiest first).  One UNet pass over K+1
+    conditioning groups and one launch that reduces them to the usual pair: the step costs about (K+1)/2 of a guided one.  Refused
+    before the seed is set: together with `text`, with n_candidate_gen_per_text > 1, at guidance_scale 1.0, an empty list, more
+    than 8 entries, a weight that is not finite, a list of the wrong length, every weight 0 at some step."""
     sampler_kw = _sampler_kwargs(sampler, negative_prompt, guidance_rescale)
+    comp_kw, make = _compose_entry(latent_diffusion, text, transcription, compose, ddim_steps, guidance_scale,
+                                   n_candidate_gen_per_text, None, "text_to_audio",
+                                   lambda p, t: make_batch_for_text_to_audio(p, transcription=t, batchsize=batchsize))
     seed_everything(int(seed))
-    batch = make_batch_for_text_to_audio(text, transcription=transcription, batchsize=batchsize)
+    batch = make() if make is not None else make_batch_for_text_to_audio(text, transcription=transcription, batchsize=batchsize)
     latent_diffusion.latent_t_size = int(duration * latent_t_per_second)
     with torch.no_grad():
         return latent_diffusion.generate_batch(batch, unconditional_guidance_scale=guidance_scale,
                                                ddim_steps=ddim_steps, n_gen=n_candidate_gen_per_text,
-                                               duration=duration, **sampler_kw)
+                                               duration=duration, **sampler_kw, **comp_kw)
 
 
 def text_to_audio_long(latent_diffusion, text, duration, overlap=2.5, transcription="", seed=42, ddim_steps=200, guidance_scale=3.5,
                        sampler=None, negative_prompt=None, guidance_rescale=0.0, loop=False, timeline=None, transition=0.0,
-                       phase=None):
+                       phase=None, compose=None):
     """Long-form text-to-audio: a clip of `duration` seconds — longer than the model's trained length — by windowed diffusion
     (LatentDiffusion.generate_batch_long): the UNet and the VAE work on windows of the model's `latent_t_size` frames that overlap
     by `overlap` seconds, fused at every step.  latent_t_size = int(duration * latent_t_per_second) must be a multiple of 8 and
@@ -1705,17 +1912,26 @@ def text_to_audio_long(latent_diffusion, text, duration, overlap=2.5, transcript
     each, so the UNet pass grows from W to R rows (generate_batch_long).  Not together with loop=True.
     `phase` (with loop=True; DESIGN.md §9k): moving window phases — "golden", or a list of ddim_steps integers in latent frames;
     the ring's windows rotate from step to step so that no frame stays a window seam (generate_batch_long).
+    `compose`: several weighted prompts on the same frames, as in text_to_audio (`text` must then be None) — every
+    window runs under all K prompts; with loop=True and `phase` as without it.  Not together with `timeline`.
     Returns np.float32 [1, 1, samples]."""
     sampler_kw = _sampler_kwargs(sampler, negative_prompt, guidance_rescale)
+    comp_kw, comp_make = _compose_entry(latent_diffusion, text, transcription, compose, ddim_steps, guidance_scale, 1, timeline,
+                                        "text_to_audio_long",
+                                        lambda p, t: make_batch_for_text_to_audio(p, transcription=t, batchsize=1))
     per_second = float(latent_diffusion.latent_t_per_second)
     latent_t = int(duration * per_second)
     hop = latent_diffusion.latent_t_size - int(round(overlap * per_second))
+    if compose is not None:
+        text = ""   # the timeline's checks below see a job without a timeline; the batches are the list's
     tl_kw, make = _timeline_entry(latent_diffusion, text, transcription, timeline, transition, loop, latent_t, hop, ddim_steps,
                                    "text_to_audio_long")
     ring = latent_diffusion.long_form_plans(latent_t, hop, ring=loop)[0]   # refuse before any GPU work
     phased_plan(ring, phase, loop, ddim_steps, latent_diffusion, "text_to_audio_long")   # ... and before the seed is set
     if phase is not None:
         tl_kw = dict(tl_kw, phase=phase)
+    if comp_make is not None:
+        tl_kw, make = dict(tl_kw, **comp_kw), comp_make
     seed_everything(int(seed))
     batch = make()
     with torch.no_grad():
@@ -1780,7 +1996,7 @@ def keep_frames(keep, per_second, latent_t):
 
 def extend_audio(latent_diffusion, text, original_audio_file_path, duration, keep=None, overlap=2.5, transcription="", seed=42,
                  ddim_steps=200, guidance_scale=3.5, sampler=None, negative_prompt=None, guidance_rescale=0.0, loop=False,
-                 timeline=None, transition=0.0, feather=0.0, phase=None, resample=None):
+                 timeline=None, transition=0.0, feather=0.0, phase=None, compose=None, resample=None):
     """Continue or inpaint a long clip: a clip of `duration` seconds — longer than the model's trained length — that keeps parts
     of the recording `original_audio_file_path` (a path, or a 1-D float waveform at 16 kHz; zero-padded or cut to `duration`) and
     generates the rest under the prompt `text` by windowed diffusion (LatentDiffusion.generate_batch_long_from_audio).  `keep`
@@ -1808,10 +2024,16 @@ def extend_audio(latent_diffusion, text, original_audio_file_path, duration, kee
     the rest new": keep=[(0, 12), (12, 15, 0.8)].  Vary a long recording, which audio_to_audio cannot: keep=[(0, 30, 0.5)].  One
     more small launch per step; pairs with feather 0 are exactly the job without levels.
     `phase` (with loop=True): moving window phases, as in text_to_audio_long; the kept source does not move.
+    `compose`: several weighted prompts for the generated part, as in text_to_audio (`text` must then be None); with
+    `keep`, `feather`, `loop`, `phase` and `resample` as without it.  Not together with `timeline`.
     Returns np.float32 [1, 1, samples]."""
     from .stft import TacotronSTFT
     from .windows import keep_levels, keep_mask
     sampler_kw = _sampler_kwargs(sampler, negative_prompt, guidance_rescale)
+    comp_kw, comp_make = _compose_entry(latent_diffusion, text, transcription, compose, ddim_steps, guidance_scale, 1, timeline,
+                                        "extend_audio", lambda p, t: make_batch_for_text_to_audio(p, transcription=t, batchsize=1))
+    if compose is not None:
+        text = ""   # the timeline's checks below see a job without a timeline; the batches are the list's
     if ddim_steps is None:
         raise ValueError("extend_audio needs ddim_steps: the ancestral sampler has no windowed form")
     if check_resample_job(resample, ddim_steps, sampler, False, latent_diffusion) is not None:
@@ -1850,8 +2072,10 @@ def extend_audio(latent_diffusion, text, original_audio_file_path, duration, kee
     seed_everything(int(seed))
     fn_STFT = TacotronSTFT(1024, 160, 1024, 64, 16000, 0, 8000)  # utils.py:262-270 "preprocessing"
     mel, _, _ = wav_to_fbank(original_audio_file_path, target_length=latent_t * f, fn_STFT=fn_STFT)
+    if comp_make is not None:
+        tl_kw, make = dict(tl_kw, **comp_kw), comp_make
     batch = make()
-    first = batch[0] if timeline is not None else batch   # the source's mel rides on the (first) batch
+    first = batch[0] if isinstance(batch, list) else batch   # the source's mel rides on the (first) batch
     first["log_mel_spec"] = first["fbank"] = mel[None, ...].float().cpu()
     with torch.no_grad():
         return latent_diffusion.generate_batch_long_from_audio(batch, latent_t, frames, hop=hop,
@@ -1869,7 +2093,9 @@ def audio_to_audio(latent_diffusion, text, original_audio_file_path, strength=0.
     that many steps are run (LatentDiffusion.generate_batch_from_audio); at strength 1 nothing of the source survives but the
     noise it was mixed into.  `negative_prompt`, `guidance_rescale` and `sampler` as in text_to_audio.  The front end is
     super_resolution_and_inpainting's (wav_to_fbank, the 16 kHz TacotronSTFT): a model whose first stage is not 16 kHz /
-    64 mel bins is refused.  Returns np.float32 [batchsize, 1, samples]."""
+    64 mel bins is refused.  Several weighted prompts (composable guidance) go through
+    LatentDiffusion.generate_batch_from_audio with a list of batches and `weights=`: this function's parameter list is pinned.
+    Returns np.float32 [batchsize, 1, samples]."""
     from .ddim import sdedit_plan
     from .stft import TacotronSTFT
     sampler_kw = _sampler_kwargs(sampler, negative_prompt, guidance_rescale)

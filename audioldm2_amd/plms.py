@@ -126,6 +126,10 @@ class PLMSSampler(SamplerBase):
             # moving window phases: every pass's gather and merge select the step's phase with the counter (both passes of the
             # eager step 0 run under row 0: the counter advances after them)
             win.step_idx = step_idx
+        if plan.compose is not None:
+            # composable guidance: the compose launch behind every pass selects the step's weights with the counter (both passes of
+            # the eager step 0 read row 0: the counter advances after them, as for cfg_rescale_indexed)
+            cond.step_idx = step_idx
 
         def guided_eps(x, t_row, out=None, idx=None, first_pass=True):
             """eps [2, b, ...] for the step kernel to combine, or with rescale the combined and rescaled [b, ...] (row: the

@@ -13,7 +13,9 @@ run that is the same whichever update rule runs.
   * resample_visits / renoise_coef / check_resample: the visit schedule and the forward-jump coefficients of resampled inpainting
     (RePaint's jumps, `resample=(n, jump)`, DESIGN.md 9i), which plan_run turns into per-visit tables for DDIM's loop;
   * keep_thresholds / hold_steps / check_levels: the per-step thresholds of graded keep levels (`graded=True`, differential
-    diffusion) and what a level means in steps; plan_run keeps the level map and the threshold rows on the device.
+    diffusion, DESIGN.md 9j) and what a level means in steps; plan_run keeps the level map and the threshold rows on the device;
+  * Composed / compose_table / check_compose_weights: K weighted conditionings on the same frames (composable guidance, DESIGN.md
+    9m) and their [V, K+1] coefficient table; model_output reduces the K+1 predictions of the group pass to the pair in one launch.
 
 What differs between the samplers stays in their modules: DDIM's graph cache on the UNet and its threaded noise feed, PLMS's eager
 Euler step 0 and its discarded `noise_like` draws, DPM-Solver++'s table per sub-range.  ddim.py re-exports every name that lived
@@ -425,6 +427,75 @@ def check_levels(mask, x0, who="graded=True"):
         raise ValueError(f"{who}: keep levels must be finite and lie in [0, 1]")
 
 
+MAX_COMPOSE = ops.MAX_COMPOSE   # prompts per composed job (ALDM_MAX_COMPOSE)
+
+
+def check_compose_weights(weights, K, who="Composed"):
+    """The weights of a composed job as an fp64 array: [K], or [S, K] — one row per sampler step in loop order, row 0
+    the noisiest.  ValueError: a shape that is neither, S == 0, a weight that is no finite number, a row whose weights are all 0
+    (the step would run K prompts to read none)."""
+    try:
+        w = np.asarray(weights, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: the weights must be numbers, [K] or [steps, K], got {weights!r}")
+    if w.ndim not in (1, 2) or w.shape[-1] != K or w.shape[0] == 0:
+        raise ValueError(f"{who}: {K} conditionings need weights of shape [{K}] or [steps, {K}], got {tuple(w.shape)}")
+    if not np.isfinite(w).all():
+        raise ValueError(f"{who}: every weight must be finite")
+    if (w.reshape(-1, K) == 0.0).all(axis=1).any():
+        raise ValueError(f"{who}: every weight is 0 at some step: the step would read no prompt")
+    return w
+
+
+class Composed:
+    """K conditionings under one set of frames with weights w_k (composable-diffusion guidance, Liu et al. 2022): the
+    `cond` of a sampler run whose model output is e_u + g * sum_k w_k (e_k - e_u).  A marker class like windows.PerPrompt.  `weights`:
+    [K], or [total_steps, K] in loop order (row 0 the noisiest step; a table over the whole schedule is cut with it: a run of its
+    last n steps reads the last n rows).  A negative weight steers away from its prompt.  The run needs an unconditional conditioning.
+    plan_run binds the run's tiled conditionings, the device table `tab` and — the sampler — the device counter `step_idx` on a copy."""
+
+    def __init__(self, conds, weights):
+        conds = list(conds)
+        if not 1 <= len(conds) <= MAX_COMPOSE:
+            raise ValueError(f"Composed: between 1 and {MAX_COMPOSE} conditionings, got {len(conds)}")
+        self.conds = conds
+        self.weights = check_compose_weights(weights, len(conds))
+        self.tab, self.step_idx = None, None
+
+    def __len__(self):
+        return len(self.conds)
+
+    def bound(self, conds, tab):
+        """A copy for one run: these (tiled) conditionings and this device table."""
+        c = Composed(conds, self.weights)
+        c.tab = tab
+        return c
+
+
+def compose_table(weights, total_steps=None, visits=None, schedule_len=None):
+    """Pure host function: the [V, K+1] fp32 coefficient table of ops.cfg_compose_indexed from a composed job's weights
+    (check_compose_weights' result).  Column 0 = 1 - sum_k w_k, formed in fp64 and rounded to fp32 once; columns 1..K = w_k.
+    Weights [K]: one row, whatever the run (the kernel clamps the counter into the table).  Weights [S, K]: S must be the run's
+    `total_steps` — or `schedule_len`, the uncut schedule's length, of which the run reads the LAST total_steps rows — and the table has
+    one row per step, or with `visits` (resample_visits) one per visit: a step visit at loop position i takes row i, a renoise visit
+    — not read — the next step visit's, blend_coef's rule.  ValueError for any other S."""
+    w = np.asarray(weights, dtype=np.float64)
+    if w.ndim == 2:
+        if total_steps is None:
+            raise ValueError("compose_table: a weight schedule needs the run's step count")
+        if w.shape[0] != total_steps:
+            if schedule_len is None or w.shape[0] != schedule_len or total_steps > schedule_len:
+                raise ValueError(f"Composed: the weight schedule has {w.shape[0]} rows, the run {total_steps} steps"
+                                 + ("" if schedule_len is None else f" (of a schedule of {schedule_len})"))
+            w = w[schedule_len - total_steps:]
+        if visits is not None:
+            w = w[np.asarray([v[1] if v[0] == "step" else v[2] for v in visits])]
+    else:
+        w = w[None]
+    tab = np.concatenate([1.0 - w.sum(axis=1, keepdims=True), w], axis=1)
+    return torch.from_numpy(np.ascontiguousarray(tab.astype(np.float32)))
+
+
 def ddim_step_rows(sigmas, alphas, alphas_prev, sqrt_one_minus_alphas):
     """Pure host function: the [S, 5] fp32 rows {sqrt(1 - a_t), sqrt(a_t), sqrt(1 - a_prev - sigma_t^2), sqrt(a_prev), sigma_t} of
     DDIM's update (the row layout of ops.ddim_step), one per schedule index, with the reference's roundings (ddim.py:330-353,
@@ -519,7 +590,13 @@ class SamplerBase(object):
         A phased ring plan (windows.with_phase, moving window phases): the same three launches in their `_ring_phased`
         forms.  All of a pass's launches read the phase of the visit from win.phase — a static int32 device table, one row per visit
         — with the device-side counter win.step_idx, so gather and merge of one pass agree and a replayed step graph moves its
-        windows without the host.  The sampler sets win.step_idx before its first step; None reads row 0."""
+        windows without the host.  The sampler sets win.step_idx before its first step; None reads row 0.
+
+        A Composed conditioning (composable guidance): one pass over the K+1 groups [uncond ; prompt 1 ; ... ; prompt K]
+        — the model's apply_model_groups on `prepared` = prepare_groups(...), or K+1 sequential apply_model calls, stacked — and
+        ops.cfg_compose_indexed in place behind it, with the row of cond.tab that the device-side counter cond.step_idx selects (None:
+        row 0): the result is the first 2n floats of the pass's output, [uncond ; composed cond] — or with use_cfg False the first
+        n, the composed prediction.  On a window plan this happens on the window rows, in front of the merge."""
         from .windows import PerPrompt, has_rows, rows_cond
         rows = win is not None and has_rows(win.plan)
         if isinstance(cond, PerPrompt):
@@ -546,6 +623,23 @@ class SamplerBase(object):
                 xw = ops.window_gather(x, win.plan, out=win.xw if static else None, **phased)
             eps_w = self.model_output(xw, t_row, win.n * b, cond, uncond, use_cfg, prepared)
             return ops.window_merge(eps_w.contiguous(), win.plan, out=win.merged if static else None, weights=win.wr, **phased)
+        if isinstance(cond, Composed):
+            # composable guidance: one pass over the K+1 groups [uncond ; prompt 1 ; ... ; prompt K], then ONE launch
+            # that reduces them to the standard pair in place — on a window plan this is the pass on the window rows, in front of
+            # the merge.  The row of the weight table is the counter's (None: row 0); the counter is read, never moved
+            if uncond is None:
+                raise ValueError("model_output: a Composed conditioning needs an unconditional conditioning (its coefficient "
+                                 "1 - sum(weights) reads it)")
+            if cond.tab is None:
+                cond.tab = compose_table(cond.weights).to(x.device)   # a direct caller: constant weights only
+            if hasattr(self.model, "apply_model_groups"):
+                if prepared is None:
+                    prepared = self.model.prepare_groups(cond.conds, uncond)
+                eps = self.model.apply_model_groups(x, t_row, prepared)
+            else:
+                tl = t_row[:b].long()
+                eps = torch.stack([self.model.apply_model(x, tl, c) for c in [uncond] + cond.conds]).contiguous()
+            return ops.cfg_compose_indexed(eps, cond.tab, cond.step_idx, pair=use_cfg)
         if not use_cfg:
             return self.model.apply_model(x, t_row[:b].long(), cond).contiguous()
         if hasattr(self.model, "apply_model_cfg"):
@@ -596,12 +690,21 @@ class SamplerBase(object):
 
         RNG contract R: x_T is the host generator's first draw of the run, made only when x_T is not given; `draw` makes the
         loop's later ones.  A start latent that already lives on the device (audio-to-audio) stays there.  Host -> device copies,
-        in this order: img, coef, t_tab, mask_d, x0_d, blend_coef, keep_thr, (a row plan's wr, a phased plan's phase,) then the
-        model's prepare_cfg."""
+        in this order: img, coef, t_tab, mask_d, x0_d, blend_coef, keep_thr, (a row plan's wr, a phased plan's phase, a Composed's
+        table,) then the model's prepare_cfg / prepare_groups.
+
+        A Composed conditioning (composable guidance): K prompts on the same frames.  It needs an unconditional
+        conditioning (ValueError otherwise, and for a weight schedule whose length is neither the run's nor the whole schedule's —
+        both before the first draw).  p.compose holds compose_table on the device — one row, or one per visit — t_tab has
+        (K+1)*W*b columns, p.cond is a bound copy with every group's conditioning tiled per window, and the model's prepare_groups
+        takes prepare_cfg's place.  The samplers point p.cond.step_idx at their step counter.  No draw is added."""
         dev = torch.device("cuda")
         shape = tuple(shape)
         from .windows import check_per_prompt, has_phase, has_rows
         check_per_prompt(cond, windows)   # a row plan and a PerPrompt conditioning go together, or neither
+        comp = isinstance(cond, Composed)   # composable guidance: K+1 UNet row groups, reduced to the pair behind the pass
+        if comp and unconditional_conditioning is None:
+            raise ValueError("a Composed conditioning needs an unconditional conditioning: its coefficient 1 - sum(weights) reads it")
         W, source = 1, None
         if windows is not None:
             if mask is not None or x0 is not None:
@@ -627,7 +730,8 @@ class SamplerBase(object):
         total_steps = ts.shape[0]
         use_cfg = not (unconditional_conditioning is None or unconditional_guidance_scale == 1.0)
         p = SimpleNamespace(total_steps=total_steps, use_cfg=use_cfg, mask_d=None, x0_d=None, blend_coef=None, prepared=None,
-                            cond=cond, uncond=unconditional_conditioning, win=None, visits=None, level_d=None, keep_thr=None)
+                            cond=cond, uncond=unconditional_conditioning, win=None, visits=None, level_d=None, keep_thr=None,
+                            compose=None)
         if resample is not None:
             if mask is None and x0 is None and source is None:
                 raise ValueError("resample= needs something to harmonise with: a mask / x0, or a source on the window plan "
@@ -640,6 +744,9 @@ class SamplerBase(object):
         if phased and int(windows.phase.numel()) != total_steps:
             raise ValueError(f"windows=: the plan's phase table has {int(windows.phase.numel())} entries, the run {total_steps} "
                              "steps: one phase per sampler step (windows.phase_table over the cut schedule)")
+        # composable guidance: the [V, K+1] coefficient table, refused here — before the first draw — when a weight schedule does not
+        # fit the run
+        compose = compose_table(cond.weights, total_steps, p.visits, len(self.ddim_timesteps)) if comp and total_steps else None
         p.time_range = np.flip(ts).copy()   # own storage, positive strides: from_numpy refuses the flipped view, even of one entry
         # guidance rescale: the combine and the per-sample rescale run in a launch of their own in front of the step kernel
         p.rescale = use_cfg and guidance_rescale > 0.0
@@ -660,7 +767,8 @@ class SamplerBase(object):
                     coef[r, 0], coef[r, 1] = renoise_coef(self.ddim_alphas, self.ddim_alphas_prev, total_steps, v[1], v[2])
             tr = tr[rows]
         p.coef = coef.to(dev)
-        p.t_tab = tr.float()[:, None].repeat(1, (2 if use_cfg else 1) * W * shape[0]).to(dev).contiguous()
+        groups = len(cond) + 1 if comp else (2 if use_cfg else 1)   # the UNet's conditioning groups
+        p.t_tab = tr.float()[:, None].repeat(1, groups * W * shape[0]).to(dev).contiguous()
         if source is not None:
             mask, x0 = source
         if mask is not None:
@@ -675,7 +783,7 @@ class SamplerBase(object):
                 p.keep_thr = keep_thresholds(total_steps, p.visits).to(dev)
         if windows is not None:
             from .windows import rows_cond, tile_cond
-            p.cond = rows_cond(cond, windows) if has_rows(windows) else tile_cond(cond, W)
+            p.cond = rows_cond(cond, windows) if has_rows(windows) else (cond if comp else tile_cond(cond, W))
             p.uncond = tile_cond(unconditional_conditioning, W)
             b, C, _, F = shape
             # blend: the plan carries a source; the fused blend-and-gather node reads x0 / mask / blend_coef from here and the
@@ -693,6 +801,13 @@ class SamplerBase(object):
                 pos = torch.arange(total_steps) if p.visits is None else \
                     torch.tensor([v[1] if v[0] == "step" else v[2] for v in p.visits], dtype=torch.long)
                 p.win.phase = windows.phase.to(torch.int32)[pos].contiguous().to(dev)
-        if use_cfg and hasattr(self.model, "apply_model_cfg") and hasattr(self.model, "prepare_cfg"):
+        if comp:
+            # the run's own copy: every group's conditioning tiled per window, and the table on the device — a static buffer of the
+            # run (of DDIM's step-graph cache entry, which refills it per job, as it refills wr and phase)
+            p.compose = compose.to(dev)
+            p.cond = cond.bound([tile_cond(c, W) for c in cond.conds] if windows is not None else cond.conds, p.compose)
+            if hasattr(self.model, "apply_model_groups") and hasattr(self.model, "prepare_groups"):
+                p.prepared = self.model.prepare_groups(p.cond.conds, p.uncond)
+        elif use_cfg and hasattr(self.model, "apply_model_cfg") and hasattr(self.model, "prepare_cfg"):
             p.prepared = self.model.prepare_cfg(p.cond, p.uncond)
         return p

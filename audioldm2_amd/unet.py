@@ -552,7 +552,8 @@ class UNetModel(nn.Module):
     @torch.no_grad()
     def forward(self, x, timesteps=None, y=None, context_list=None, context_attn_mask_list=None, cfg_shared=False, **kwargs):
         """openaimodel.py:837-885.  x: [N, C, H, W] fp32 on the GPU; returns eps [N, C_out, H, W] (cfg_shared: x [B, ...] once for
-        the 2B rows [uncond ; cond] of a classifier-free-guidance pass, returns eps [2B, ...]; see below)."""
+        the 2B rows [uncond ; cond] of a classifier-free-guidance pass — or the G*B rows of G conditioning groups — returns eps
+        [G*B, ...]; see below)."""
         assert (y is not None) == self.use_extra_film_by_concat, \
             "must specify y if and only if the model is class-conditional or film embedding conditional"
         if not x.is_cuda:
@@ -566,15 +567,21 @@ class UNetModel(nn.Module):
         # context the two halves compute identical values — conv_in, the level-0 ResBlocks, the first Downsample, the first
         # level-1 ResBlock, the context-free first transformer — so that prefix runs on B samples and its output (and its skip
         # tensors, when the decoder pops them) is duplicated: 4 of 7 level-0 convs at half the rows, ~0.5 ms of a 22 ms step.
+        # G conditioning groups (composable guidance, DESIGN.md 9m: [uncond ; prompt 1 ; ... ; prompt K], G = K + 1): the same
+        # argument holds for every group, so the prefix still runs once on B samples and its output and skips are repeated G times.
+        # G = the contexts' (or y's) rows over B; 2 is the guided pass above, unchanged.
         div = self._shared_prefix_end(context_list) if cfg_shared else None
         B = x.shape[0]
+        G = 2
         if cfg_shared:
-            assert timesteps.shape[0] in (B, 2 * B) and all(c is None or c.shape[0] == 2 * B for c in context_list), \
-                "cfg_shared: x [B, ...] once, contexts for the 2B rows [uncond ; cond]"
+            rows = [c.shape[0] for c in context_list if c is not None] + ([y.shape[0]] if y is not None else [])
+            G = rows[0] // B if rows else 2
+            assert G >= 2 and timesteps.shape[0] in (B, G * B) and all(r == G * B for r in rows), \
+                "cfg_shared: x [B, ...] once, contexts for the G*B rows [uncond ; cond ...] of G >= 2 groups"
             timesteps = timesteps[:B]
             if div is None:   # FiLM-conditioned model (y differs between the halves from the first ResBlock on): nothing to share
-                x = x.repeat(2, 1, 1, 1)
-                timesteps = timesteps.repeat(2)
+                x = x.repeat(G, 1, 1, 1)
+                timesteps = timesteps.repeat(G)
         t_emb = ops.timestep_embedding(timesteps, self.model_channels)
         emb = ops.linear(ops.linear(t_emb, pk["te0"], act=ACT_SILU), pk["te2"])
         if self.use_extra_film_by_concat:
@@ -588,7 +595,7 @@ class UNetModel(nn.Module):
                 h = module.run(h, emb, context_list, mask_list)
                 hs.append(h)
         else:
-            dup = lambda t: t.repeat(2, *([1] * (t.dim() - 1)))   # rows [B, 2B) = rows [0, B)
+            dup = lambda t: t.repeat(G, *([1] * (t.dim() - 1)))   # rows [g*B, (g+1)*B) = rows [0, B)
             emb_half, emb = emb, _EmbSlices(dup(emb_rows))
             for bi, module in enumerate(self.input_blocks):
                 if bi < div[0]:

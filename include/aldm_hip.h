@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 /* ---- library / error ------------------------------------------------------------------ */
-int aldm_version(void);              /* ABI version (26),bumped on any struct / entry change */
+int aldm_version(void);              /* ABI version (27),bumped on any struct / entry change */
 const char* aldm_last_error(void);   /* message of the last failing call on this thread     */
 
 /* ---- activations usable as prologue (applied to the gathered input) or epilogue -------- */
@@ -578,6 +578,24 @@ int aldm_dpmpp_sde_step_indexed(float* x, const float* eps, float* x0_buf, const
  * [1, n] model output (coef[6] == 0).                                                                                            */
 int aldm_cfg_rescale_indexed(const float* eps, float* out, const float* coef_tab, const int* step_idx, int B, int64_t n_s,
                              int coef_ld, void* stream);
+/* Composable guidance (Liu et al. 2022, "Compositional Visual Generation with Composable Diffusion Models"; ABI v27):
+ * the K+1 predictions of one UNet pass reduced to the standard [uncond ; cond] pair, one launch behind the pass.  eps holds
+ * [(K+1), n]: group 0 the unconditional prediction, groups 1..K the prompts'.  w_tab holds [rows, K+1] floats: column 0 is
+ * c_0 = 1 - sum_k w_k (formed in fp64 on the host, rounded once), columns 1..K are c_k = w_k.  r = clamp(step_idx ? *step_idx : 0,
+ * 0, rows - 1) — the blend-gather entries' conventions for the counter.  The row's coefficients are read once per thread.
+ *   e_c[i] = sum_g c_g * eps[g*n + i]   over ascending g,   == e_u + sum_k w_k (e_k - e_u)
+ * A group whose coefficient is exactly 0 is skipped before its element is loaded (a NaN there cannot reach the output, and it costs no
+ * traffic); the first kept term is a plain multiply, every later one one fused multiply-add; no kept term gives 0.  K = 1, w = 1
+ * makes e_c bitwise eps[1].  pair == 1: out[0:n] = eps[0] bitwise, out[n:2n] = e_c — the pair every step kernel,
+ * aldm_cfg_rescale_indexed and the window merge take.  pair == 0 (no guidance): out[0:n] = e_c.  out == eps is allowed (in place: a
+ * thread owns element i of every group and stores after it has loaded them all; group 0 is not rewritten under pair == 1); any other
+ * overlap of out with eps, and any overlap of out with w_tab, is refused.  16-byte accesses when n % 4 == 0 and eps and out are
+ * 16-byte aligned, else a scalar form; grid-stride, 64-bit indexing; no atomics: the result does not depend on the launch geometry.
+ * Refused before any launch: null eps / out / w_tab, K outside [1, ALDM_MAX_COMPOSE], rows < 1, pair outside {0, 1}, n outside
+ * (0, 2^40], the overlaps above.                                                                                                  */
+#define ALDM_MAX_COMPOSE 8
+int aldm_cfg_compose_indexed(const float* eps, float* out, const float* w_tab, const int* step_idx, int rows, int K, int pair,
+                             int64_t n, void* stream);
 /* *step_idx += 1 and t_cur[0..nt) = t_tab[min(*step_idx, steps-1)] (the next step's timestep row, the UNet's static input;
  * the time_range of ddim.py:205-213 stored as floats, one row per step in loop order)                                  */
 int aldm_step_advance(int* step_idx, const float* t_tab, float* t_cur, int nt, int steps, void* stream);
