@@ -1797,36 +1797,26 @@ def posterior_qsample(moments_cl: torch.Tensor, n_post: torch.Tensor, n_enc: tor
     return z, x_t
 
 
-def _window_starts(plan) -> "_l.WindowStarts":
-    """plan.starts as the by-value kernel argument (built once per plan)."""
+def _has_rows(plan) -> bool:
+    return getattr(plan, "rows", None) is not None
+
+
+def _window_starts(plan):
+    """The starts of `plan` as the by-value kernel argument, built once per plan: the row starts of a row plan (windows.row_plan) as
+    a WindowRows, else plan.starts as a WindowStarts."""
     st = getattr(plan, "_starts_arg", None)
     if st is None:
-        if len(plan.starts) > _l.MAX_WINDOWS:
-            raise RuntimeError(f"window plan: {len(plan.starts)} windows, at most {_l.MAX_WINDOWS}")
-        st = _l.WindowStarts()
-        st.n = len(plan.starts)
-        for j, s in enumerate(plan.starts):
+        if _has_rows(plan):
+            starts, st, most, what = plan.row_starts, _l.WindowRows(), _l.MAX_ROWS, "row plan: {} rows"
+        else:
+            starts, st, most, what = plan.starts, _l.WindowStarts(), _l.MAX_WINDOWS, "window plan: {} windows"
+        if len(starts) > most:
+            raise RuntimeError(f"{what.format(len(starts))}, at most {most}")
+        st.n = len(starts)
+        for j, s in enumerate(starts):
             st.s[j] = int(s)
         plan._starts_arg = st
     return st
-
-
-def _window_rows(plan) -> "_l.WindowRows":
-    """A row plan's row starts (windows.row_plan) as the by-value kernel argument (built once per plan)."""
-    st = getattr(plan, "_rows_arg", None)
-    if st is None:
-        if len(plan.row_starts) > _l.MAX_ROWS:
-            raise RuntimeError(f"row plan: {len(plan.row_starts)} rows, at most {_l.MAX_ROWS}")
-        st = _l.WindowRows()
-        st.n = len(plan.row_starts)
-        for r, s in enumerate(plan.row_starts):
-            st.s[r] = int(s)
-        plan._rows_arg = st
-    return st
-
-
-def _has_rows(plan) -> bool:
-    return getattr(plan, "rows", None) is not None
 
 
 def _window_groups(plan) -> int:
@@ -1834,10 +1824,9 @@ def _window_groups(plan) -> int:
     return plan.R if _has_rows(plan) else plan.W
 
 
-def _window_entry(plan, name: str):
-    """The C entry of a window launch: `name`, or its wrap-around form `name`_ring for a ring plan (windows.window_plan(...,
-    ring=True); the argument lists are the same)."""
-    return getattr(_l.load(), name + "_ring" if getattr(plan, "ring", False) else name)
+def _chk_step_idx(step_idx: Optional[torch.Tensor], what: str) -> None:
+    if step_idx is not None and (step_idx.dtype != torch.int32 or not step_idx.is_cuda or step_idx.numel() != 1):
+        raise RuntimeError(f"{what}.step_idx: expected one int32 on the device")
 
 
 def _has_phase(plan) -> bool:
@@ -1863,9 +1852,24 @@ def _window_phase(plan, phase: Optional[torch.Tensor], step_idx: Optional[torch.
     if not (torch.is_tensor(phase) and phase.is_cuda and phase.dtype == torch.int32 and phase.dim() == 1 and phase.numel() >= 1
             and phase.is_contiguous()):
         raise RuntimeError(f"{what}.phase: expected a contiguous 1-D int32 CUDA table with at least one row")
-    if step_idx is not None and (step_idx.dtype != torch.int32 or not step_idx.is_cuda or step_idx.numel() != 1):
-        raise RuntimeError(f"{what}.step_idx: expected one int32 on the device")
+    _chk_step_idx(step_idx, what)
     return phase
+
+
+def _window_call(plan, name: str, what: str, head, tab, counter, lead, B: int, C: int, T: int, F: int) -> None:
+    """Launch the form of the C entry `name` that `plan` takes — the one place where that is decided.  A phased ring plan (`tab`, its
+    phase table from _window_phase, is not None): `name`_ring_phased, which takes the table, `counter` (the step counter, where
+    it does not stand in `head` already) and the table's rows behind the starts.  A row plan (windows.row_plan): `name`_rows,
+    which counts its rows in the starts and takes no window count.  Else `name`, or its wrap-around form `name`_ring for a ring
+    plan (windows.window_plan(..., ring=True); the argument lists are the same).  `head`: the arguments in front of the starts;
+    `lead`: what stands between the starts (and the phase) and B."""
+    if tab is not None:
+        form, mid = "_ring_phased", (tab.data_ptr(),) + tuple(counter) + (tab.numel(),) + tuple(lead) + (B, plan.W)
+    elif _has_rows(plan):
+        form, mid = "_rows", tuple(lead) + (B,)
+    else:
+        form, mid = "_ring" if getattr(plan, "ring", False) else "", tuple(lead) + (B, plan.W)
+    _l.check(getattr(_l.load(), name + form)(*head, _window_starts(plan), *mid, C, T, plan.Tw, F, _stream()), what)
 
 
 def _no_overlap(out: torch.Tensor, what: str, others) -> None:
@@ -1897,17 +1901,7 @@ def window_gather(x: torch.Tensor, plan, out: Optional[torch.Tensor] = None, pha
         raise RuntimeError(f"window_gather.out: expected {shape}, got {tuple(out.shape)}")
     _no_overlap(out, "window_gather.out", [(x, "x")])
     tab = _window_phase(plan, phase, step_idx, "window_gather", x.device)
-    if tab is not None:
-        _l.check(_l.load().aldm_window_gather_ring_phased(x.data_ptr(), out.data_ptr(), _window_starts(plan), tab.data_ptr(),
-                                                          _p(step_idx), tab.numel(), B, plan.W, C, T, plan.Tw, F, _stream()),
-                 "window_gather")
-        return out
-    if _has_rows(plan):
-        _l.check(_l.load().aldm_window_gather_rows(x.data_ptr(), out.data_ptr(), _window_rows(plan), B, C, T, plan.Tw, F, _stream()),
-                 "window_gather")
-        return out
-    _l.check(_window_entry(plan, "aldm_window_gather")(x.data_ptr(), out.data_ptr(), _window_starts(plan), B, plan.W, C, T, plan.Tw, F,
-                                          _stream()), "window_gather")
+    _window_call(plan, "aldm_window_gather", "window_gather", (x.data_ptr(), out.data_ptr()), tab, (_p(step_idx),), (), B, C, T, F)
     return out
 
 
@@ -1941,8 +1935,7 @@ def window_blend_gather(x: torch.Tensor, x0: torch.Tensor, qnoise: torch.Tensor,
     if blend_coef.numel() < 2 or blend_coef.shape[-1] != 2 or blend_coef.dim() > 2:
         raise RuntimeError(f"window_blend_gather.blend_coef: expected [coef_rows, 2], got {tuple(blend_coef.shape)}")
     coef_rows = blend_coef.numel() // 2
-    if step_idx is not None and (step_idx.dtype != torch.int32 or not step_idx.is_cuda or step_idx.numel() != 1):
-        raise RuntimeError("window_blend_gather.step_idx: expected one int32 on the device")
+    _chk_step_idx(step_idx, "window_blend_gather")
     shape = (_window_groups(plan) * B, C, plan.Tw, F)
     if out is None:
         out = torch.empty(shape, device=x.device, dtype=torch.float32)
@@ -1953,21 +1946,9 @@ def window_blend_gather(x: torch.Tensor, x0: torch.Tensor, qnoise: torch.Tensor,
     _no_overlap(out, "window_blend_gather.out", [(x, "x")] + others + [(blend_coef, "blend_coef")])
     _no_overlap(x, "window_blend_gather.x", others + [(blend_coef, "blend_coef")])
     tab = _window_phase(plan, phase, step_idx, "window_blend_gather", x.device)
-    if tab is not None:
-        _l.check(_l.load().aldm_window_blend_gather_ring_phased(x.data_ptr(), x0.data_ptr(), qnoise.data_ptr(), mask.data_ptr(),
-                                                                blend_coef.data_ptr(), _p(step_idx), q_rows, coef_rows,
-                                                                out.data_ptr(), _window_starts(plan), tab.data_ptr(), tab.numel(),
-                                                                B, plan.W, C, T, plan.Tw, F, _stream()), "window_blend_gather")
-        return out
-    if _has_rows(plan):
-        _l.check(_l.load().aldm_window_blend_gather_rows(x.data_ptr(), x0.data_ptr(), qnoise.data_ptr(), mask.data_ptr(),
-                                                         blend_coef.data_ptr(), _p(step_idx), q_rows, coef_rows, out.data_ptr(),
-                                                         _window_rows(plan), B, C, T, plan.Tw, F, _stream()), "window_blend_gather")
-        return out
-    _l.check(_window_entry(plan, "aldm_window_blend_gather")(x.data_ptr(), x0.data_ptr(), qnoise.data_ptr(), mask.data_ptr(),
-                                                blend_coef.data_ptr(), _p(step_idx), q_rows, coef_rows, out.data_ptr(),
-                                                _window_starts(plan), B, plan.W, C, T, plan.Tw, F, _stream()),
-             "window_blend_gather")
+    _window_call(plan, "aldm_window_blend_gather", "window_blend_gather",
+                 (x.data_ptr(), x0.data_ptr(), qnoise.data_ptr(), mask.data_ptr(), blend_coef.data_ptr(), _p(step_idx), q_rows,
+                  coef_rows, out.data_ptr()), tab, (), (), B, C, T, F)
     return out
 
 
@@ -2009,17 +1990,8 @@ def window_merge(win: torch.Tensor, plan, out: Optional[torch.Tensor] = None, we
         wn = weights
     _no_overlap(out, "window_merge.out", [(win, "win"), (wn, "wn")])
     tab = _window_phase(plan, phase, step_idx, "window_merge", win.device)
-    if tab is not None:
-        _l.check(_l.load().aldm_window_merge_ring_phased(win.data_ptr(), wn.data_ptr(), out.data_ptr(), _window_starts(plan),
-                                                         tab.data_ptr(), _p(step_idx), tab.numel(), H, B, plan.W, C, plan.T, plan.Tw,
-                                                         F, _stream()), "window_merge")
-        return out
-    if _has_rows(plan):
-        _l.check(_l.load().aldm_window_merge_rows(win.data_ptr(), wn.data_ptr(), out.data_ptr(), _window_rows(plan), H, B, C, plan.T,
-                                                  plan.Tw, F, _stream()), "window_merge")
-        return out
-    _l.check(_window_entry(plan, "aldm_window_merge")(win.data_ptr(), wn.data_ptr(), out.data_ptr(), _window_starts(plan), H, B, plan.W, C,
-                                         plan.T, plan.Tw, F, _stream()), "window_merge")
+    _window_call(plan, "aldm_window_merge", "window_merge", (win.data_ptr(), wn.data_ptr(), out.data_ptr()), tab,
+                 (_p(step_idx),), (H,), B, C, plan.T, F)
     return out
 
 

@@ -13,7 +13,12 @@ jobs per arm (default 5), the arms alternating job by job.
     (2, (160, 64, 48), 1, 64) — the one shape of the tests where a launch is not launch-bound: GPU time per launch from events around
     --reps back-to-back launches.
 Per-step GPU time from events recorded by the step callback, median over the replayed steps (from the fourth step on) (sample_log
-only: no VAE, no vocoder).  A measurement, not a bar.  Prints one JSON object; --out also writes it."""
+only: no VAE, no vocoder).  A measurement, not a bar.  Prints one JSON object; --out also writes it.
+
+--launches-only skips 1 and 2 (no model is built) and times in 3, next to the ring and phased launches, the launches of the linear
+plan of the same key and of a row plan over it (three prompts), each from 16-byte aligned tensors and from tensors one float off
+(the scalar path): every window kernel of csrc/windows.hip at both access widths.  With $ALDM_LIB_PATH naming another build of the
+library, one such process per build compares the two builds launch by launch."""
 import argparse
 import json
 import os
@@ -37,15 +42,18 @@ def main():
     ap.add_argument("--T", type=int, default=768)
     ap.add_argument("--hop", type=int, default=192)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--launches-only", action="store_true")
     args = ap.parse_args()
     import torch
     from audioldm2_amd import lib, ops
     from audioldm2_amd.pipeline import build_model, seed_everything
-    from audioldm2_amd.windows import phase_table, window_plan, with_phase
+    from audioldm2_amd.windows import phase_table, prompt_weights, row_plan, window_plan, with_phase
     from oracle import cases
     lib.load()
-    ld = build_model(model_name="audioldm2-full").cuda()
-    ld.latent_t_size = 256
+    ld = None
+    if not args.launches_only:
+        ld = build_model(model_name="audioldm2-full").cuda()
+        ld.latent_t_size = 256
     ring = window_plan(args.T, 256, args.hop, ring=True)
     short = window_plan(256, 256, 192, ring=True)
     phased = with_phase(ring, phase_table(ring, args.steps, "golden"))
@@ -88,26 +96,47 @@ def main():
         torch.cuda.synchronize()
         return round(a.elapsed_time(b) * 1e3 / args.reps, 3)
 
-    def launches(key, B, C, F, row=1):
-        """The three launches of the ring plan `key` and of the same plan under the golden table, read at row `row`."""
+    def launches(key, B, C, F, row=1, shift=0, every_plan=False):
+        """The three launches of the ring plan `key` and of the same plan under the golden table, read at row `row`; every_plan:
+        of the linear plan `key` and of a row plan over it too.  shift = 1: every tensor starts one float off a 16-byte boundary."""
         r = window_plan(*key, ring=True)
         p = with_phase(r, phase_table(r, args.steps, "golden"))
         tab, idx = p.phase.cuda(), torch.full((1,), row, device="cuda", dtype=torch.int32)
-        x = torch.randn(B, C, r.T, F, device="cuda")
-        x0, qn, mask = torch.randn_like(x), torch.randn_like(x), (torch.rand_like(x) > 0.5).float()
+
+        def randn(*shape):
+            n = 1
+            for d in shape:
+                n *= d
+            return torch.randn(n + shift, device="cuda")[shift:].view(shape)
+        x = randn(B, C, r.T, F)
+        x0, qn, mask = randn(*x.shape), randn(*x.shape), randn(*x.shape).gt_(0)
         coef = torch.tensor([0.8, 0.6], device="cuda")
-        xw = torch.empty(r.W * B, C, r.Tw, F, device="cuda")
-        eps = torch.randn(2, r.W * B, C, r.Tw, F, device="cuda")
-        out = torch.empty(2, B, C, r.T, F, device="cuda")
-        t = {"ring": {"gather_us": launch_us(lambda: ops.window_gather(x, r, out=xw)),
-                      "merge_us": launch_us(lambda: ops.window_merge(eps, r, out=out)),
-                      "blend_gather_us": launch_us(lambda: ops.window_blend_gather(x, x0, qn, mask, coef, r, out=xw))},
-             "phased": {"gather_us": launch_us(lambda: ops.window_gather(x, p, out=xw, phase=tab, step_idx=idx)),
-                        "merge_us": launch_us(lambda: ops.window_merge(eps, p, out=out, phase=tab, step_idx=idx)),
-                        "blend_gather_us": launch_us(lambda: ops.window_blend_gather(x, x0, qn, mask, coef, p, step_idx=idx, out=xw,
-                                                                                     phase=tab))}}
-        return dict(t, key=list(key), B=B, C=C, F=F, W=r.W, starts=list(r.starts), phase=int(p.phase[row]),
+
+        def three(plan, **kw):
+            G = plan.R if getattr(plan, "rows", None) is not None else plan.W
+            xw, eps, out = randn(G * B, C, plan.Tw, F), randn(2, G * B, C, plan.Tw, F), randn(2, B, C, plan.T, F)
+            return {"gather_us": launch_us(lambda: ops.window_gather(x, plan, out=xw, **kw)),
+                    "merge_us": launch_us(lambda: ops.window_merge(eps, plan, out=out, **kw)),
+                    "blend_gather_us": launch_us(lambda: ops.window_blend_gather(x, x0, qn, mask, coef, plan, out=xw,
+                                                                                 step_idx=kw.get("step_idx"), phase=kw.get("phase")))}
+        t = {"ring": three(r), "phased": three(p, phase=tab, step_idx=idx)}
+        if every_plan:
+            lin = window_plan(*key)
+            rows = row_plan(lin, prompt_weights(lin.T, [lin.T // 3, 2 * lin.T // 3], lin.Tw // 4))
+            t.update({"linear": three(lin), "rows": three(rows), "R": rows.R})
+        return dict(t, key=list(key), B=B, C=C, F=F, W=r.W, starts=list(r.starts), phase=int(p.phase[row]), shift=shift,
                     phased_over_ring={k: round(t["phased"][k] / t["ring"][k], 4) for k in t["ring"]})
+
+    shapes = [((args.T, 256, args.hop), 1, 8, 16), ((160, 64, 48), 2, 1, 64)]
+    if args.launches_only:
+        res = {"what": "every window launch alone, on the step's shapes and on the mel case, aligned and one float off",
+               "device": torch.cuda.get_device_name(0), "lib": lib.LIB_PATH, "reps": args.reps,
+               "launches_alone": [launches(*sh, shift=shift, every_plan=True) for shift in (0, 1) for sh in shapes]}
+        print(json.dumps(res))
+        if args.out:
+            with open(args.out, "w") as f:
+                json.dump(res, f, indent=1)
+        return
 
     res = {"what": "DDIM step of a seamless loop under moving window phases (the golden table) next to the same loop on the fixed "
                    "ring, at 30 s and at the trained length: replayed steps, batch 1, eta 0; and each phased launch alone next to "
@@ -130,7 +159,7 @@ def main():
                 "ring_repeat_spread": spread("ring"),
                 "phased_256_over_ring_256": round(med["phased_256"] / med["ring_256"], 4),
                 "ring_256_repeat_spread": spread("ring_256"),
-                "launches_alone": [launches((args.T, 256, args.hop), 1, 8, 16), launches((160, 64, 48), 2, 1, 64)]})
+                "launches_alone": [launches(*sh) for sh in shapes]})
     print(json.dumps(res))
     if args.out:
         with open(args.out, "w") as f:
